@@ -23,12 +23,16 @@ reference's own FaceMesh test image, upscaled; see load_patch) at a seeded posit
 whose detector finds nothing are tracked on a seeded square ROI ("forced-ROI mode", SURVEY.md
 §8d C3).
 
-Prints ONE JSON line (rank 0).  At N = 1 it also carries:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the `--steps` steps, writes
+the last step's results when `--dump-outputs DIR` is given, and prints the line.  With `--full`,
+at N = 1, the line also carries:
   * "hand": config 4 (palm lite + hand landmark lite, 4 ROIs per frame, 256 frames per step);
   * "cpu_baseline": the oracle's C restatement of the same pipeline, P single-threaded
     processes on the host cores, timed before the GPU is touched;
   * "roofline": the dominant kernel, from an uncontended (one-stream) profiled pass, with the
-    rocprofv3 PMC traffic of that kernel; "pipeline_roofline": SURVEY §8d's per-frame model.
+    rocprofv3 PMC traffic of that kernel;
+  * the side lines "face_next", "tracking", "face_loop", "hand_tracking", "config5", "jpeg_source".
+"pipeline_roofline" (SURVEY §8d's per-frame model over the timed steps) is in every line.
 `--workload hand` benchmarks config 4 alone; `--workload both` runs face and hand pipelines
 concurrently on their own HIP streams with one combined all-gather (config 5).
 """
@@ -132,7 +136,20 @@ def parse():
                          "over a one-rank communicator), to price it on one GPU")
     ap.add_argument("--prime-seconds", type=float, default=0.6,
                     help="untimed pipeline priming before the warmup steps (see prime())")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure at N = 1: the CPU baseline, the "
+                         "per-kernel profiled pass and its rocprofv3 traffic passes, and the side lines "
+                         "(hand, face_next, tracking, config 5, JPEG); the --no-* options pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (detections, ROIs, landmarks) as "
+                         "DIR/<name>.npy (float32), see dump_outputs()")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        for leg in ("cpu_baseline", "profile", "traffic", "hand", "next", "tracking", "jpeg", "c5"):
+            setattr(args, "no_" + leg, True)
+    return args
 
 
 # ---------------------------------------------------------------- synthetic frames
@@ -433,6 +450,53 @@ def run_steps(workloads, steps, gather, rank, world, pool):
     return [w.pipe.times() for w in workloads]
 
 
+def _rrect(r):
+    return list(r.rect().tuple()) + [r.rotation_radians()]
+
+
+def dump_outputs(dirname, workloads, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last step, per pipeline
+    `<kind>` (face | hand | face_next), as float32 arrays (a few MB: nothing is sampled):
+      <kind>_detections.npy [D, 7 + 2K]  frame, confidence, angle, rect (cx, cy, w, h), K keypoints (x, y)
+      <kind>_rois.npy       [R, 16]      frame, from_detection, tracked, confidence, raw_handedness,
+                                         tongue_out, roi (cx, cy, w, h, rad), next_roi (the same 5)
+      <kind>_landmarks.npy  [R, L, 3]    landmarks in frame coordinates
+      <kind>_world.npy      [R, Lw, 3]   metric landmarks (hand network only)
+    An array that would be empty (no detection at all; world landmarks of a face network) is
+    not written.  Rows follow the pipeline's own order (frames ascending).  A lost ROI (tracked = 0) has no
+    estimate: its landmark rows, next_roi, raw_handedness and tongue_out are 0.  With N > 1 every
+    rank writes its own frames' results as <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for w in workloads:
+        p = w.pipe
+        dets = [(f, d) for f, ds in enumerate(p.detections()) for d in ds]
+        nk = max([len(d.keypoints()) for _, d in dets], default=0)
+        da = np.zeros((len(dets), 7 + 2 * nk), np.float32)
+        for i, (f, d) in enumerate(dets):
+            kps = [c for kp in d.keypoints() for c in kp]
+            da[i, :7] = [f, d.confidence(), d.angle(), *d.bounding_rect().tuple()]
+            da[i, 7:7 + len(kps)] = kps
+        rois = [p.roi(i) for i in range(p.num_rois())]
+        nl = max([r["landmarks"].shape[0] for r in rois], default=0)
+        nw = max([r["world"].shape[0] for r in rois], default=0)
+        ra = np.zeros((len(rois), 16), np.float32)
+        lm = np.zeros((len(rois), nl, 3), np.float32)
+        wd = np.zeros((len(rois), nw, 3), np.float32)
+        for i, r in enumerate(rois):
+            ra[i, :4] = [r["frame"], r["from_detection"], r["tracked"], r["confidence"]]
+            ra[i, 6:11] = _rrect(r["roi"])
+            if r["tracked"]:
+                ra[i, 4:6] = [r["raw_handedness"], r["tongue_out"]]
+                ra[i, 11:16] = _rrect(r["next_roi"])
+                lm[i, :r["landmarks"].shape[0]] = r["landmarks"]
+                wd[i, :r["world"].shape[0]] = r["world"]
+        for name, a in (("detections", da), ("rois", ra), ("landmarks", lm), ("world", wd)):
+            if a.size == 0:  # nothing to compare: no detection at all, or a network without world landmarks
+                continue
+            np.save(os.path.join(dirname, f"{w.kind}_{name}{suffix}.npy"), a)
+
+
 def main():
     args = parse()
     from zaru_amd import launch
@@ -531,6 +595,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wls, rank, world)
 
     counts = np.array([[t["tracked"], t["rois"], t["frames"], t["detections"]] for t in times], np.float64)
     gather_check = None

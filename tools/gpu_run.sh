@@ -14,9 +14,9 @@ for s in ${STEPS//,/ }; do
   case $s in
     tests) timeout -k 10 500 python -u -m pytest tests -m gpu -v -rP --timeout 120 --timeout-method thread > $O/pytest.log 2>&1 ;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ;;
-    bench) timeout -k 10 700 python bench.py "$@" > $O/bench.json 2> $O/bench.err ;;
-    quick) timeout -k 10 300 python bench.py --no-cpu-baseline --no-traffic $NOSIDE "$@" > $O/quick.json 2> $O/quick.err ;;
-    hand) timeout -k 10 300 python bench.py --workload hand --batch 256 --steps 30 --warmup 5 --no-cpu-baseline --no-traffic "$@" > $O/hand.json 2> $O/hand.err ;;
+    bench) timeout -k 10 700 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err ;;
+    quick) timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-traffic $NOSIDE "$@" > $O/quick.json 2> $O/quick.err ;;
+    hand) timeout -k 10 300 python bench.py --full --workload hand --batch 256 --steps 30 --warmup 5 --no-cpu-baseline --no-traffic "$@" > $O/hand.json 2> $O/hand.err ;;
     both) timeout -k 10 300 python bench.py --workload both --steps 30 --warmup 5 --no-cpu-baseline --no-traffic --no-profile "$@" > $O/both.json 2> $O/both.err ;;
     n1) timeout -k 10 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-traffic --no-profile $NOSIDE "$@" > $O/n1.json 2> $O/n1.err ;;
     n1g) timeout -k 10 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-traffic --no-profile --self-gather $NOSIDE "$@" > $O/n1g.json 2> $O/n1g.err ;;
@@ -34,10 +34,10 @@ for s in ${STEPS//,/ }; do
     n2half) ZARU_BENCH_SHARE_GPU=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
           --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --batch 512 --steps 50 --warmup 10 \
           --no-cpu-baseline --no-traffic --no-profile $NOSIDE "$@" > $O/n2half.json 2> $O/n2half.err ;;
-    jpeg) timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-traffic --no-profile \
+    jpeg) timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-traffic --no-profile \
           --no-hand --no-next --no-tracking --no-c5 "$@" > $O/jpeg.json 2> $O/jpeg.err ;;
     prof) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py \
-          --steps 20 --warmup 5 --no-cpu-baseline --no-traffic $NOSIDE "$@" > $O/bench_prof.json 2> $O/prof.err ;;
+          --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic $NOSIDE "$@" > $O/bench_prof.json 2> $O/prof.err ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
   rc=$?
