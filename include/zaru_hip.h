@@ -138,6 +138,27 @@ int zr_detect_post_mapped_async(const float *d_logits, const float *d_boxes, con
                                 const zr_detpost_cfg *cfg, int32_t *d_count, float *d_dets, size_t dcap,
                                 int32_t *d_ties, void *hip_stream);
 
+/* ---- Face recognition: embedding matching --------------------------------------------------
+ * Embedding::difference (examples/eval_face_recognition.rs:31-42) of every query against every
+ * gallery row, and each query's nearest row.  d_query is [q][dim] and d_gallery [g][dim] f32,
+ * row-major, on the device.  The distance of a pair is bit-exact with the reference: d = a[k] -
+ * b[k], s = s + d * d for k = 0 .. dim-1 in order from s = 0 (multiply and add rounded
+ * separately), then a correctly rounded sqrt.
+ *   d_best_idx[i]  the gallery row nearest to query i: the smallest distance, the lowest row among
+ *                  equal distances; a NaN distance never wins.  -1 when g == 0, when the query is
+ *                  masked out, or when every distance is NaN.
+ *   d_best_dist[i] that row's distance, +inf where d_best_idx[i] is -1.
+ *   d_dist         may be NULL; else [q][g], every distance (+inf in the rows of masked queries).
+ *   d_valid        may be NULL; else int32 per query, 0 masks the query out (a pipeline passes its
+ *                  per-frame detection counts).
+ * The embedding network's output of a batch ([n][128]) is a valid d_query / d_gallery as it is.
+ * Refused (ZR_ERR_INVALID_ARGUMENT, nothing launched): q == 0, dim == 0, NULL d_query /
+ * d_best_idx / d_best_dist, NULL d_gallery with g > 0, and q, g, dim or the 64 x 64 tile count
+ * beyond 2^31 - 1 (the kernel indexes rows and tiles with 32 bits). */
+int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery, size_t g, size_t dim,
+                         const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist,
+                         float *d_dist /* [q][g], may be NULL */, void *hip_stream);
+
 /* ---- the one collective of the multi-GPU path ------------------------------
  * A communicator over the node's ranks (one process per GPU) for the all-gather of the detection
  * records (RCCL over xGMI).  The reference has no multi-device code; this is the build's own
@@ -345,8 +366,10 @@ int zr_profile_enable(zr_session *s, int enable);
 int zr_profile_read(zr_session *s, char *buf, size_t cap, size_t *needed);
 
 /* Compile a model without a GPU and describe the fused launch plan as text, one launch per
- * line (for tests and diagnostics).  Writes at most `cap` bytes incl. the NUL terminator;
- * `*needed` receives the full length + 1. */
+ * line (for tests and diagnostics).  A line starts with the step kind: gemm, dw, direct (generic
+ * dense conv; "direct stem" is the stem kernel, which can sample RGBA frames itself), elt,
+ * resize, gap, dwpw, dwgap, gdc (depthwise over the whole plane).  Writes at most `cap` bytes
+ * incl. the NUL terminator; `*needed` receives the full length + 1. */
 int zr_plan_describe(const uint8_t *onnx, size_t len, const uint32_t *out_sel, size_t n_sel,
                      char *buf, size_t cap, size_t *needed);
 

@@ -62,6 +62,7 @@ SIGNATURES = [
     ("zr_track_seed_detections_async", _I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _F, _I, _P, _P, _P, _P]),
     ("zr_hand_manage_async", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, C.c_double, _I,
                                   _P, _P, _P]),
+    ("zr_embed_match_async", _I, [_P, _SZ, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),
     ("zr_comm_destroy", None, [_P]),

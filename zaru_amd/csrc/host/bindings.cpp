@@ -10,6 +10,7 @@
 #include "device_hand_tracker.h"
 #include "landmark.h"
 #include "pipeline.h"
+#include "recognition.h"
 #include "device_face_loop.h"
 #include "device_tracker.h"
 
@@ -634,4 +635,124 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("stream", [](const DetectTrackPipeline &p) { return reinterpret_cast<uint64_t>(p.stream()); })
         .def("profile", &DetectTrackPipeline::profile)
         .def("profile_read", &DetectTrackPipeline::profile_read);
+
+    // ---- face recognition (examples/eval_face_recognition.rs)
+    auto model_vec = [](const py::bytes &b) {
+        const std::string s = b;
+        return std::vector<uint8_t>(s.begin(), s.end());
+    };
+    auto embedding_of = [](const py::array_t<float, py::array::c_style> &a) {
+        if ((size_t)a.size() != EMBEDDING_DIM) throw ZaruError(ZR_ERR_SHAPE, "an embedding is 128 floats");
+        Embedding e;
+        std::memcpy(e.v.data(), a.data(), EMBEDDING_DIM * sizeof(float));
+        return e;
+    };
+    auto embedding_array = [](const Embedding &e) {
+        py::array_t<float> a((py::ssize_t)EMBEDDING_DIM);
+        std::memcpy(a.mutable_data(), e.v.data(), EMBEDDING_DIM * sizeof(float));
+        return a;
+    };
+    auto device_frames = [](const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames) {
+        std::vector<Image> im;
+        for (auto &f : frames) {
+            Image i;
+            i.rgba = reinterpret_cast<const uint8_t *>(std::get<0>(f));
+            i.width = std::get<1>(f);
+            i.height = std::get<2>(f);
+            i.row_stride = std::get<3>(f);
+            i.on_device = true;
+            im.push_back(i);
+        }
+        return im;
+    };
+    m.attr("NO_MATCH") = NO_MATCH;
+    py::class_<Embedding>(m, "Embedding")
+        .def(py::init(embedding_of))
+        .def("difference", &Embedding::difference)
+        .def("values", embedding_array);
+    py::class_<FaceEmbedder>(m, "FaceEmbedder")
+        .def(py::init([model_vec](const py::bytes &model, int device) { return new FaceEmbedder(model_vec(model), device); }),
+             py::arg("model"), py::arg("device") = 0)
+        .def("input_width", [](const FaceEmbedder &e) { return e.cnn().input_width(); })
+        .def("session", [](const FaceEmbedder &e) { return reinterpret_cast<uint64_t>(e.cnn().nn().handle()); })
+        .def("crop_view", &FaceEmbedder::crop_view)
+        .def("embed", [](const FaceEmbedder &e, py::array_t<uint8_t, py::array::c_style> img, const std::vector<Rect> &rects) {
+            const auto v = e.embed(host_image(img), rects);
+            py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)EMBEDDING_DIM});
+            for (size_t i = 0; i < v.size(); i++)
+                std::memcpy(a.mutable_data() + i * EMBEDDING_DIM, v[i].v.data(), EMBEDDING_DIM * sizeof(float));
+            return a;
+        })
+        .def("embed_first_face", [embedding_array](const FaceEmbedder &e, Detector &d,
+                                                   py::array_t<uint8_t, py::array::c_style> img) -> py::object {
+            Embedding out;
+            if (!e.embed_first_face(d, host_image(img), out)) return py::none();
+            return embedding_array(out);
+        });
+    py::class_<Gallery>(m, "Gallery")
+        .def(py::init<int, size_t>(), py::arg("device") = 0, py::arg("dim") = EMBEDDING_DIM)
+        .def("__len__", &Gallery::size)
+        .def("size", &Gallery::size)
+        .def("clear", &Gallery::clear)
+        .def("add", [](Gallery &g, py::array_t<float, py::array::c_style> rows, const std::vector<uint64_t> &ids) {
+            if ((size_t)rows.size() != ids.size() * g.dim()) throw ZaruError(ZR_ERR_SHAPE, "rows must be [len(ids)][dim]");
+            g.add(rows.data(), ids.data(), ids.size());
+        })
+        .def("match", [](Gallery &g, py::array_t<float, py::array::c_style> queries) {
+            if (queries.size() % (py::ssize_t)g.dim()) throw ZaruError(ZR_ERR_SHAPE, "queries must be [q][dim]");
+            const size_t q = (size_t)queries.size() / g.dim();
+            py::array_t<uint64_t> ids((py::ssize_t)q);
+            py::array_t<float> dist((py::ssize_t)q);
+            g.match(queries.data(), q, ids.mutable_data(), dist.mutable_data());
+            return py::make_tuple(ids, dist);
+        });
+    py::class_<FaceRecognizer>(m, "FaceRecognizer")
+        .def(py::init([model_vec](const py::bytes &model, const std::string &detector, int device, size_t chunk,
+                                  float det_threshold) {
+                 return new FaceRecognizer(model_vec(model), detector_net(detector), device, chunk, det_threshold);
+             }), py::arg("model"), py::arg("detector") = "face", py::arg("device") = 0, py::arg("chunk") = 256,
+             py::arg("det_threshold") = Detector::DEFAULT_THRESHOLD)
+        .def("session", [](const FaceRecognizer &r) {
+            return reinterpret_cast<uint64_t>(r.embedder().cnn().nn().handle());
+        })
+        // frames: (device pointer, width, height, row stride) of RGBA images in HBM -> found [n] bool,
+        // embeddings [n][128] (zeros where not found), ids [n] (NO_MATCH where none), distances [n]
+        .def("recognize", [device_frames](FaceRecognizer &r, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
+                                          const Gallery &g) {
+            const std::vector<Image> im = device_frames(frames);
+            std::vector<Recognition> res;
+            {
+                py::gil_scoped_release nogil;
+                res = r.recognize(im, g);
+            }
+            const py::ssize_t n = (py::ssize_t)res.size();
+            py::array_t<bool> found(n);
+            py::array_t<float> emb({n, (py::ssize_t)EMBEDDING_DIM}), dist(n);
+            py::array_t<uint64_t> ids(n);
+            for (py::ssize_t i = 0; i < n; i++) {
+                found.mutable_data()[i] = res[i].found;
+                std::memcpy(emb.mutable_data() + i * EMBEDDING_DIM, res[i].embedding.v.data(), EMBEDDING_DIM * sizeof(float));
+                ids.mutable_data()[i] = res[i].id;
+                dist.mutable_data()[i] = res[i].distance;
+            }
+            return py::make_tuple(found, emb, ids, dist);
+        })
+        .def("enqueue", [device_frames](FaceRecognizer &r, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
+                                        const Gallery &g) {
+            const std::vector<Image> im = device_frames(frames);
+            py::gil_scoped_release nogil;
+            r.enqueue(im, g);
+        })
+        .def("synchronize", &FaceRecognizer::synchronize, py::call_guard<py::gil_scoped_release>())
+        // the crop views the device built: [n][8] f32 sampling parameters and [n] frame indices
+        .def("views", [](FaceRecognizer &r) {
+            const auto v = r.views();
+            py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)8});
+            py::array_t<uint32_t> f((py::ssize_t)v.size());
+            for (size_t i = 0; i < v.size(); i++) {
+                std::memcpy(a.mutable_data() + 8 * i, &v[i], 8 * sizeof(float));
+                f.mutable_data()[i] = v[i].frame;
+            }
+            return py::make_tuple(a, f);
+        });
 }

@@ -1,0 +1,109 @@
+// recognition.h -- face recognition as crates/zaru/examples/eval_face_recognition.rs does it:
+// detect a face, crop it (the detection rect grown by 40 %, fitted to the network's aspect), embed
+// the crop as 128 floats (MobileFaceNet), compare embeddings by Euclidean distance.
+//   Embedding       the example's `Embedding` with `difference` (lines 31-42)
+//   FaceEmbedder    the example's `FaceEmbedder` (lines 44-93) over a model given as bytes
+//   Gallery         device-resident embeddings with caller ids, nearest-row matching
+//   FaceRecognizer  the whole chain over frames resident in HBM, no host decision between stages
+// Links only against the C ABI, like the rest of host/.
+#pragma once
+#include <array>
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "detection.h"
+#include "networks.h"
+
+namespace zh {
+
+constexpr size_t EMBEDDING_DIM = 128;
+constexpr uint64_t NO_MATCH = UINT64_MAX;
+
+struct Embedding {
+    std::array<float, EMBEDDING_DIM> v{};
+    // eval_face_recognition.rs:31-42: sqrt of the sum over k, in order, of (a[k] - b[k])^2
+    float difference(const Embedding &o) const;
+};
+
+class FaceEmbedder {
+  public:
+    static constexpr float CROP_GROW = 0.4f;  // eval_face_recognition.rs:85
+    explicit FaceEmbedder(const std::vector<uint8_t> &model, int device = 0);
+    const Cnn &cnn() const { return *cnn_; }
+    // the crop of one face: rect.grow_rel(0.4).grow_to_fit_aspect(input aspect) as a view of the
+    // whole image (lines 82-91; a Rect is a rotation-0 view, image/mod.rs:151-156)
+    ViewData crop_view(uint32_t image_w, uint32_t image_h, const Rect &rect) const;
+    std::vector<Embedding> embed(const Image &img, const std::vector<Rect> &rects) const;
+    // the example's loop body for one image: the first detection (NMS order); false when none
+    bool embed_first_face(Detector &detector, const Image &img, Embedding &out) const;
+
+  private:
+    std::shared_ptr<const Cnn> cnn_;
+};
+
+class Gallery {
+  public:
+    explicit Gallery(int device = 0, size_t dim = EMBEDDING_DIM);
+    ~Gallery();
+    Gallery(const Gallery &) = delete;
+    Gallery &operator=(const Gallery &) = delete;
+    size_t size() const { return ids_.size(); }
+    size_t dim() const { return dim_; }
+    // rows: n * dim floats (host)
+    void add(const float *rows, const uint64_t *ids, size_t n);
+    void clear() { ids_.clear(); }
+    // queries: q * dim floats (host); ids[i] = NO_MATCH and distances[i] = +inf without a match
+    void match(const float *queries, size_t q, uint64_t *ids, float *distances);
+    const float *device_rows() const { return rows_ ? rows_->ptr : nullptr; }
+    uint64_t id_of(int32_t row) const { return row < 0 || (size_t)row >= ids_.size() ? NO_MATCH : ids_[row]; }
+
+  private:
+    size_t dim_;
+    void *stream_ = nullptr;
+    std::unique_ptr<DeviceArray<float>> rows_;
+    size_t cap_ = 0;  // rows allocated
+    std::vector<uint64_t> ids_;
+};
+
+struct Recognition {
+    bool found = false;  // a face was detected in the frame
+    Embedding embedding; // zeros when !found
+    uint64_t id = NO_MATCH;
+    float distance = 0.f;  // +inf without a match
+};
+
+class FaceRecognizer {
+  public:
+    // `chunk` frames run per launch sequence (bounds the activation arenas)
+    FaceRecognizer(const std::vector<uint8_t> &model, DetectorNetwork detector, int device = 0, size_t chunk = 256,
+                   float det_thresh = Detector::DEFAULT_THRESHOLD);
+    ~FaceRecognizer();
+    FaceRecognizer(const FaceRecognizer &) = delete;
+    FaceRecognizer &operator=(const FaceRecognizer &) = delete;
+    const FaceEmbedder &embedder() const { return emb_; }
+    // frames: device-resident RGBA images.  Enqueues everything, then one copy back.
+    std::vector<Recognition> recognize(const std::vector<Image> &frames, const Gallery &gallery);
+    // the same without the copy back (benchmarks): results stay in HBM until the next call
+    void enqueue(const std::vector<Image> &frames, const Gallery &gallery);
+    void synchronize();
+    // the crop views the device built for the last call's frames
+    std::vector<zr_view_desc> views();
+
+  private:
+    FaceEmbedder emb_;
+    DetectorNetwork det_net_;
+    std::shared_ptr<const Cnn> det_;
+    size_t chunk_;
+    zr_detpost_cfg pcfg_{};
+    zr_track_cfg tcfg_{};
+    void *stream_ = nullptr;
+    size_t n_ = 0;
+    DeviceArray<float> anchors_, det_boxes_, det_logits_, dets_, lbox_, emb_out_, best_dist_;
+    DeviceArray<uint32_t> fsize_;
+    DeviceArray<int32_t> count_, best_idx_;
+    DeviceArray<zr_track_state> state_;
+    DeviceArray<zr_view_desc> views_;
+};
+
+}  // namespace zh

@@ -73,37 +73,44 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemParams P) {
     }
     __syncthreads();
     const int ly = threadIdx.x / STW, lx = threadIdx.x - ly * STW;
-    f32x2 acc[CO / 2];
-#pragma unroll
-    for (int o = 0; o < CO / 2; ++o) acc[o] = (f32x2)(0.f);
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int ky = 0; ky < K; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < K; ++kx) {
-                const float v = patch[c][ly * S + ky][lx * S + kx];
-                // weights [3][K][K][32]: uniform, so scalar loads feeding v_pk_fma_f32
-                const f32x2 *w2 = (const f32x2 *)(P.w + ((c * K + ky) * K + kx) * 32);
-#pragma unroll
-                for (int o = 0; o < CO / 2; ++o) acc[o] = __builtin_elementwise_fma(w2[o], (f32x2)(v), acc[o]);
-            }
     const int oy = ty0 + ly, ox = tx0 + lx;
-    if (oy >= P.OH || ox >= P.OW) return;
-    float vo[CO];
+    // CO <= 32: every output channel of the pixel in registers.  CO = 64 (MobileFaceNet's stem):
+    // two passes of 32 channels over the one staged patch, so the accumulators stay at 32.
+    constexpr int CP = CO <= 32 ? 32 : 64, CG = CO <= 32 ? CO : 32;
+#pragma unroll 1
+    for (int c0 = 0; c0 < CO; c0 += CG) {
+        f32x2 acc[CG / 2];
 #pragma unroll
-    for (int o = 0; o < CO / 2; ++o) {
-        vo[2 * o] = acc[o].x + P.bias[2 * o];
-        vo[2 * o + 1] = acc[o].y + P.bias[2 * o + 1];
+        for (int o = 0; o < CG / 2; ++o) acc[o] = (f32x2)(0.f);
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int ky = 0; ky < K; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) {
+                    const float v = patch[c][ly * S + ky][lx * S + kx];
+                    // weights [3][K][K][CP]: uniform, so scalar loads feeding v_pk_fma_f32
+                    const f32x2 *w2 = (const f32x2 *)(P.w + ((c * K + ky) * K + kx) * CP + c0);
+#pragma unroll
+                    for (int o = 0; o < CG / 2; ++o) acc[o] = __builtin_elementwise_fma(w2[o], (f32x2)(v), acc[o]);
+                }
+        if (oy >= P.OH || ox >= P.OW) continue;
+        float vo[CG];
+#pragma unroll
+        for (int o = 0; o < CG / 2; ++o) {
+            vo[2 * o] = acc[o].x + P.bias[c0 + 2 * o];
+            vo[2 * o + 1] = acc[o].y + P.bias[c0 + 2 * o + 1];
+        }
+        apply_act_n<CG>(P.act, vo, [c0](int o) { return c0 + o; });
+        float *dst = P.out + (int64_t)n * P.o_sN + (int64_t)c0 * P.o_sC + (int64_t)oy * P.OW + ox;
+#pragma unroll
+        for (int o = 0; o < CG; ++o)
+            if (c0 + o < P.Cout) dst[(int64_t)o * P.o_sC] = vo[o];
     }
-    apply_act_n<CO>(P.act, vo, [](int o) { return o; });
-    float *dst = P.out + (int64_t)n * P.o_sN + (int64_t)oy * P.OW + ox;
-#pragma unroll
-    for (int o = 0; o < CO; ++o)
-        if (o < P.Cout) dst[(int64_t)o * P.o_sC] = vo[o];
 }
 
 bool stem_supported(int cin, int k, int stride, int cout) {
-    return cin == 3 && (k == 3 || k == 5) && (stride == 1 || stride == 2) && cout >= 1 && cout <= 32;
+    return cin == 3 && (k == 3 || k == 5) && (stride == 1 || stride == 2) && cout >= 1 &&
+           cout <= (k == 3 ? 64 : 32);
 }
 
 template <int K, int S, int CO>
@@ -119,6 +126,8 @@ template <int K, int S>
 static const char *stem_co(const StemParams &p, bool pre, hipStream_t s) {
     if (p.Cout <= 16) return stem_go<K, S, 16>(p, pre, s);
     if (p.Cout <= 24) return stem_go<K, S, 24>(p, pre, s);
+    if constexpr (K == 3)
+        if (p.Cout > 32) return stem_go<K, S, 64>(p, pre, s);
     return stem_go<K, S, 32>(p, pre, s);
 }
 

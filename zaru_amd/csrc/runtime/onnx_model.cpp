@@ -208,6 +208,13 @@ bool parse_attr(Reader r, OnnxAttr &a) {
         case 2: memcpy(&a.f, &f.v, 4); break;
         case 3: a.i = (int64_t)f.v; break;
         case 4: a.s = str(f); break;
+        case 5:  // t (a Constant node's value)
+            if (f.wire == 2) {
+                std::string tname, terr;
+                if (!parse_tensor(sub(f), tname, a.t, terr)) return false;
+                a.has_t = true;
+            }
+            break;
         case 7:
             if (f.wire == 5) {
                 float v;
@@ -340,6 +347,28 @@ bool parse_onnx(const uint8_t *data, size_t len, OnnxModel &m, std::string &err)
         err = "malformed GraphProto";
         return false;
     }
+    // A Constant node with an f32 or int64 `value` tensor is an initializer under its output
+    // name (Clip bounds, Reshape targets and Pad amounts are then found like any other).  Every
+    // other form (sparse_value, value_float(s), value_int(s), value_string(s), a dtype the loader
+    // cannot hold) is refused by name.
+    std::vector<OnnxNode> kept;
+    for (auto &nd : m.nodes) {
+        if (nd.op != "Constant") {
+            kept.push_back(std::move(nd));
+            continue;
+        }
+        const OnnxAttr *v = nd.attr("value");
+        const std::string who = "Constant " + (nd.name.empty() && !nd.out.empty() ? nd.out[0] : nd.name);
+        if (nd.out.size() != 1 || nd.out[0].empty()) return err = who + ": needs exactly one output", false;
+        if (!v || !v->has_t) return err = who + ": only a `value` tensor attribute is supported", false;
+        const OnnxTensor &t = v->t;
+        const bool f32 = t.dtype == 1 && (int64_t)t.f.size() == t.numel();
+        const bool i64 = t.dtype == 7 && (int64_t)t.i64.size() == t.numel();
+        if (!f32 && !i64) return err = who + ": value must be an f32 or int64 tensor", false;
+        if (m.inits.count(nd.out[0])) return err = who + ": output redefines an initializer", false;
+        m.inits[nd.out[0]] = t;
+    }
+    m.nodes = std::move(kept);
     for (auto &vi : all_inputs)
         if (!m.inits.count(vi.name)) m.inputs.push_back(vi);
     return true;

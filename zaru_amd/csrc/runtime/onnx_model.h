@@ -10,6 +10,21 @@
 
 namespace zr {
 
+struct OnnxTensor {
+    std::vector<int64_t> dims;
+    int dtype = 0;             // TensorProto.DataType: 1 float, 7 int64, 10 float16
+    std::vector<float> f;      // float / float16 data (converted to f32)
+    std::vector<int64_t> i64;  // int64 data
+    // element count; only meaningful after parse_tensor validated the dims (each >= 0, product
+    // <= kMaxTensorElems), so it cannot overflow
+    int64_t numel() const {
+        int64_t n = 1;
+        for (auto d : dims) n *= d;
+        return n;
+    }
+    static constexpr int64_t kMaxTensorElems = int64_t(1) << 30;  // 4 GiB of f32
+};
+
 struct OnnxAttr {
     std::string name;
     float f = 0.f;
@@ -17,6 +32,9 @@ struct OnnxAttr {
     std::string s;
     std::vector<int64_t> ints;
     std::vector<float> floats;
+    // the `t` tensor of a Constant node's `value` attribute
+    bool has_t = false;
+    OnnxTensor t;
 };
 
 struct OnnxNode {
@@ -44,21 +62,6 @@ struct OnnxNode {
         auto a = attr(n);
         return a ? a->s : std::string(d);
     }
-};
-
-struct OnnxTensor {
-    std::vector<int64_t> dims;
-    int dtype = 0;             // TensorProto.DataType: 1 float, 7 int64, 10 float16
-    std::vector<float> f;      // float / float16 data (converted to f32)
-    std::vector<int64_t> i64;  // int64 data
-    // element count; only meaningful after parse_tensor validated the dims (each >= 0, product
-    // <= kMaxTensorElems), so it cannot overflow
-    int64_t numel() const {
-        int64_t n = 1;
-        for (auto d : dims) n *= d;
-        return n;
-    }
-    static constexpr int64_t kMaxTensorElems = int64_t(1) << 30;  // 4 GiB of f32
 };
 
 struct OnnxValueInfo {

@@ -468,10 +468,20 @@ bool Compiler::lower_conv(const OnnxNode &nd) {
     const bool patch = g == 1 && kh == kw && st[0] == kh && st[1] == kw && kh >= 2 && kh <= 4 &&
                        pads[0] == 0 && pads[1] == 0 && pads[2] == 0 && pads[3] == 0 &&
                        H % kh == 0 && W % kw == 0 && !fullplane;
+    // depthwise over the whole plane (MobileFaceNet's global depthwise conv, 7x7 on 7^2): one
+    // output per (image, channel)
+    const bool dw_plane = g == Cin && Mo == Cin && Cg == 1 && kh == H && kw == W && OH == 1 && OW == 1 &&
+                          st[0] == 1 && st[1] == 1 && pads[0] == 0 && pads[1] == 0 && pads[2] == 0 &&
+                          pads[3] == 0 && gdc_supported(H, W);
     if (depthwise) {
         s.kind = S_DW;
         s.w_off = push_weights(w->f);
         s.b_off = push_weights(bias);
+    } else if (dw_plane) {
+        s.kind = S_GDC;
+        s.w_off = push_weights(w->f);
+        s.b_off = push_weights(bias);
+        s.bytes = 4.0 * ((double)Cin * H * W + Mo);
     } else if (pointwise || fullplane || patch) {
         s.kind = S_GEMM;
         s.in2 = TRef{};
@@ -491,11 +501,12 @@ bool Compiler::lower_conv(const OnnxNode &nd) {
         s.M = Mo;
         s.stem = kh == kw && stem_supported(Cin, kh, (int)st[0], Mo);
         std::vector<float> wf = w->f;
-        if (s.stem) {  // stem_kernel: [Cin][kh][kw][32], output channel innermost, zero-padded
-            wf.assign((size_t)32 * Cin * kh * kw, 0.f);
+        if (s.stem) {  // stem_kernel: [Cin][kh][kw][CP], output channel innermost, zero-padded
+            const int CP = stem_cpad(Mo);
+            wf.assign((size_t)CP * Cin * kh * kw, 0.f);
             for (int m = 0; m < Mo; m++)
-                for (int t = 0; t < Cin * kh * kw; t++) wf[(size_t)t * 32 + m] = w->f[(size_t)m * Cin * kh * kw + t];
-            bias.resize(32, 0.f);
+                for (int t = 0; t < Cin * kh * kw; t++) wf[(size_t)t * CP + m] = w->f[(size_t)m * Cin * kh * kw + t];
+            bias.resize(CP, 0.f);
         }
         s.w_off = push_weights(wf);
         s.b_off = push_weights(bias);
@@ -582,10 +593,10 @@ bool Compiler::lower_act(const OnnxNode &nd) {
         Step &s = P.steps[x.step];
         ActDesc a;
         const bool gemm = s.kind == S_GEMM || s.kind == S_DWPW;
-        const int Cpad = gemm ? s.Mpad : (s.stem ? std::max(C, 32) : C);
+        const int Cpad = gemm ? s.Mpad : (s.stem ? stem_cpad(C) : C);
         ActDesc *slot = nullptr;
         if (gemm) slot = s.res_mode ? &s.post : (s.pre.kind ? nullptr : &s.pre);
-        else if (s.kind == S_DW || s.kind == S_DIRECT || s.kind == S_ELT) slot = s.pre.kind ? nullptr : &s.pre;
+        else if (s.kind == S_DW || s.kind == S_DIRECT || s.kind == S_ELT || s.kind == S_GDC) slot = s.pre.kind ? nullptr : &s.pre;
         if (gemm && s.res_mode && s.post.kind) slot = nullptr;
         if (slot) {
             if (!act_from_node(nd, C, Cpad, a)) return false;
@@ -1417,6 +1428,23 @@ void run_plan(const Plan &plan, const Binding &b, hipStream_t stream, LaunchHook
             d.bias = W + s.b_off;
             d.act = act_of(s.pre, W);
             kname = launch_dwgap(d, stream);
+            break;
+        }
+        case S_GDC: {
+            DwParams d{};
+            d.in = plane_of(s.in, plan, b);
+            d.out = const_cast<float *>(out.p);
+            d.o_sN = out.sN;
+            d.o_sC = out.sC;
+            d.OH = 1;
+            d.OW = 1;
+            d.N = b.N;
+            d.k = s.kh;
+            d.stride = 1;
+            d.w = W + s.w_off;
+            d.bias = W + s.b_off;
+            d.act = act_of(s.pre, W);
+            kname = launch_gdc(d, stream);
             break;
         }
         case S_GAP: {

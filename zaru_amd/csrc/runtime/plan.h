@@ -20,7 +20,9 @@ namespace zr {
 
 // S_DWGAP: a depthwise conv (S_DW fields) whose only consumer was a global average pool; `out`
 // is the pooled vector
-enum StepKind { S_GEMM, S_DW, S_DIRECT, S_ELT, S_RESIZE, S_GAP, S_DWPW, S_DWGAP };
+// S_GDC: a depthwise conv whose kernel is its whole input plane (pad 0): `out` is a per-image
+// vector (gdc.hip)
+enum StepKind { S_GEMM, S_DW, S_DIRECT, S_ELT, S_RESIZE, S_GAP, S_DWPW, S_DWGAP, S_GDC };
 
 struct TRef {
     int kind = 0;  // 0 internal storage, 1 graph input, 2 graph output
@@ -54,7 +56,7 @@ struct Step {
     ActDesc dw_act;
     // S_DWGAP: the depthwise output plane (pooled away)
     int dw_oh = 0, dw_ow = 0;
-    // S_DIRECT: runs as stem_kernel (Cin = 3, weights padded to 32 output channels)
+    // S_DIRECT: runs as stem_kernel (Cin = 3, weights padded to 32 or 64 output channels)
     bool stem = false;
     // algorithmic traffic / work per image (for roofline accounting); bytes_pre: the same
     // step sampling its input from RGBA frames (4 B per input pixel instead of 12)

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -410,7 +411,7 @@ int zr_plan_describe(const uint8_t *onnx, size_t len, const uint32_t *out_sel, s
         zr::Plan plan;
         std::vector<uint32_t> sel(out_sel, out_sel + n_sel);
         if (!zr::compile_plan(m, sel, plan, err)) return set_err(ZR_ERR_MODEL, err);
-        static const char *kinds[] = {"gemm", "dw", "direct", "elt", "resize", "gap", "dwpw", "dwgap"};
+        static const char *kinds[] = {"gemm", "dw", "direct", "elt", "resize", "gap", "dwpw", "dwgap", "gdc"};
         static const char *acts[] = {"none", "relu", "clip", "prelu", "sigmoid"};
         std::string t;
         char line[512];
@@ -994,6 +995,59 @@ int zr_preprocess_views_async(const zr_frame *frames, size_t n_frames, const zr_
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipFreeAsync(dv, st));
         HIP_TRY(hipFreeAsync(df, st));
+        return ZR_OK;
+    });
+}
+
+namespace {
+struct MatchScratch {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+std::mutex g_match_mu;
+std::map<hipStream_t, MatchScratch> g_match_scratch;
+}  // namespace
+
+int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery, size_t g, size_t dim,
+                         const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist, float *d_dist,
+                         void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_query || !d_best_idx || !d_best_dist || (g > 0 && !d_gallery))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null query, gallery or output pointer");
+        if (q == 0 || dim == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "no queries or zero embedding dimension");
+        const size_t lim = 0x7fffffffu;
+        if (q > lim || g > lim || dim > lim || ((q + 63) / 64) * ((g + 63) / 64) > lim)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "queries x gallery beyond the kernel's 32-bit row and tile indices; split it");
+        hipStream_t st = (hipStream_t)hip_stream;
+        zr::MatchParams p{};
+        p.q = d_query;
+        p.g = d_gallery;
+        p.Q = (int)q;
+        p.G = (int)g;
+        p.D = (int)dim;
+        p.valid = d_valid;
+        p.best_idx = d_best_idx;
+        p.best_dist = d_best_dist;
+        p.dist = d_dist;
+        // Per-tile partial results, reduced by the launch's second pass.  One buffer per stream,
+        // grown on demand and kept: plain hipMalloc memory, like every other buffer one kernel
+        // writes and the next reads.  (With stream-ordered pool memory -- hipMallocAsync per call --
+        // the second pass read stale keys on the MI355X: tiles computed on other XCDs were missing.)
+        const size_t scratch = zr::embed_match_scratch(p.Q, p.G);
+        std::lock_guard<std::mutex> lock(g_match_mu);  // both launches of a call stay adjacent
+        MatchScratch &ms = g_match_scratch[st];
+        if (scratch > ms.bytes) {
+            if (ms.ptr) {
+                HIP_TRY(hipStreamSynchronize(st));  // earlier calls on this stream still read it
+                HIP_TRY(hipFree(ms.ptr));
+                ms = MatchScratch{};
+            }
+            HIP_TRY(hipMalloc(&ms.ptr, scratch));
+            ms.bytes = scratch;
+        }
+        p.keys = static_cast<unsigned long long *>(ms.ptr);
+        zr::launch_embed_match(p, st);
+        HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
 }

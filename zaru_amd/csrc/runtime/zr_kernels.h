@@ -154,6 +154,21 @@ struct CandParams {
     float *rec;              // [N][cap][2 + D]
 };
 
+// ---------------------------------------------------------------- embedding matching (match.hip)
+// Euclidean distance of every query against every gallery row (rows of D floats) and each
+// query's nearest row.  Q, G and Q-tiles x G-tiles fit 31 bits (the C ABI checks).
+struct MatchParams {
+    const float *q, *g;          // [Q][D], [G][D]
+    int Q, G, D;
+    const int32_t *valid;        // [Q] or null: a query with valid == 0 matches nothing
+    unsigned long long *keys;    // scratch of embed_match_scratch(Q, G) bytes (may be null when G == 0)
+    int32_t *best_idx;           // [Q]
+    float *best_dist;            // [Q]
+    float *dist;                 // [Q][G] or null
+};
+size_t embed_match_scratch(int Q, int G);
+const char *launch_embed_match(const MatchParams &p, hipStream_t s);
+
 // ---------------------------------------------------------------- fused kernels (fused.hip)
 // Dense KxK stride-S stem conv with Cin = 3 (every model's first layer).  With `pre` the
 // kernel samples its input from RGBA frames through per-image views (K1 fused in front);
@@ -165,8 +180,9 @@ struct StemParams {
     int64_t o_sN, o_sC;
     int IH, IW, OH, OW, N, Cout;
     int k, stride, pad_t, pad_l;
-    const float *w;      // [3][k][k][32] (output channel innermost, zero-padded to 32)
-    const float *bias;   // [>= 32]
+    const float *w;      // [3][k][k][CP] (output channel innermost, zero-padded to CP =
+                         // stem_cpad(Cout))
+    const float *bias;   // [>= CP]
     Act act;
     const int *nact;     // as GemmParams::nact
 };
@@ -204,6 +220,9 @@ enum Form : int { FORM_DMA, FORM_V4, FORM_VALU, FORM_VALU_DB, FORM_ROWS, FORM_VR
 bool form_on(Form f);
 
 bool stem_supported(int cin, int k, int stride, int cout);
+inline int stem_cpad(int cout) { return cout <= 32 ? 32 : 64; }
+// the full-plane depthwise (gdc.hip) stages 256 planes in LDS
+inline bool gdc_supported(int h, int w) { return h * w >= 2 && h * w <= 64; }
 bool dwpw_supported(int k, int stride);
 
 // launchers (kernels/*.hip); each returns the symbol of the kernel it launched
@@ -221,6 +240,9 @@ const char *launch_gap(const GapParams &p, hipStream_t s);
 // depthwise + activation + global average pool in one launch (out / o_sN / o_sC: the pooled
 // vector); planes of <= 512 floats (64 of them staged in LDS)
 const char *launch_dwgap(const DwParams &p, hipStream_t s);
+// depthwise conv whose kernel is the whole input plane (k x k = H x W, pad 0, stride 1): out /
+// o_sN / o_sC address the per-image vector; OH = OW = 1 (gdc.hip)
+const char *launch_gdc(const DwParams &p, hipStream_t s);
 const char *launch_preproc(const PreprocParams &p, hipStream_t s);
 const char *launch_candidates(const CandParams &p, hipStream_t s);
 const char *launch_stem(const StemParams &p, bool pre, hipStream_t s);
