@@ -228,6 +228,52 @@ int zr_track_seed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *c
 int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
                           const float *d_landmarks, size_t lm_stride, const float *d_flag,
                           size_t flag_stride, float *d_lm_out, zr_view_desc *d_views, void *hip_stream);
+
+/* ---- Landmark temporal filters (crates/zaru/src/filter, landmark.rs:142-202) on the device ----
+ * Estimator::set_filter smooths the network's landmarks over time, per landmark and coordinate,
+ * between extract and the map-out, so the tracked RoI follows the filtered landmarks.  In a
+ * device loop that is two calls between the network and the next frame:
+ *     zr_lm_filter_async               extract + filter, positions in network pixels
+ *     zr_track_update_positions_async  zr_track_update_async on those positions
+ * The arithmetic is the reference's, f32 in its operation order with correctly rounded division
+ * and no contraction, so it is bit-identical to the host restatement (host/filter.cpp):
+ *     EMA         alpha * v + (1 - alpha) * last                                   (ema.rs:41)
+ *     alpha-beta  pred = x + v * dt; res = value - pred; x = pred + alpha * res;
+ *                 v += (beta * res) / dt                                   (alpha_beta.rs:52-58)
+ *     1 euro      a(c) = r / (r + 1) with r = ((2 pi) * c) * dt; dx = (v - x) / dt;
+ *                 dx^ = a(d_cutoff) * dx + (1 - a(d_cutoff)) * dx^prev;
+ *                 x = a(c) * v + (1 - a(c)) * x with c = min_cutoff + beta * |dx^|
+ *                                                                            (one_euro.rs:74-98)
+ * A value's first sample passes through and primes its state.  Time is explicit: elapsed_s is
+ * the seconds since the previous call (the reference's TimedFilterAdapter is not restated). */
+enum { ZR_LM_FILTER_NONE = 0, ZR_LM_FILTER_EMA = 1, ZR_LM_FILTER_ALPHA_BETA = 2, ZR_LM_FILTER_ONE_EURO = 3 };
+typedef struct {
+    int kind;   /* ZR_LM_FILTER_* */
+    float p[3]; /* EMA {alpha}; alpha-beta {alpha, beta}; 1 euro {min_cutoff, beta, d_cutoff};
+                   alpha and beta in [0, 1] (1 euro: min_cutoff > 0, beta >= 0), else
+                   ZR_ERR_INVALID_ARGUMENT */
+} zr_lm_filter;
+/* Bytes of filter state per stream (0 for ZR_LM_FILTER_NONE); stream i's state starts at
+ * d_filter_state + i * bytes.  The layout is opaque; all-zero bytes are the default ("no value
+ * seen") state, so a hipMemsetAsync resets it. */
+int zr_lm_filter_state_size(const zr_lm_filter *filter, size_t num_landmarks, size_t *bytes);
+/* For each of the n streams: the kind's extract of cfg (as zr_track_update_async reads output 0 /
+ * output 1, same stride rules), every coordinate (z included) filtered, the result in
+ * d_positions (n x L x 3, network pixels) and the state updated in place.  A stream whose
+ * d_state[i].active == 0 is skipped: its filter state keeps every byte and its d_positions row
+ * is NaN (d_state == NULL: every stream is active).  ZR_LM_FILTER_NONE only extracts
+ * (d_filter_state may be NULL).  elapsed_s must be finite and > 0 for the time-based filters
+ * (alpha-beta, 1 euro), which divide by it. */
+int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, const zr_track_state *d_state,
+                       size_t n, const float *d_landmarks, size_t lm_stride, const float *d_flag,
+                       size_t flag_stride, float elapsed_s, void *d_filter_state, float *d_positions,
+                       void *hip_stream);
+/* zr_track_update_async on already extracted positions (n x L x 3, network pixels: what
+ * zr_lm_filter_async wrote) instead of the raw landmark output.  The confidence still comes from
+ * d_flag for kinds 0/1 (kinds 2/3: d_flag may be NULL); everything else is the same update. */
+int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                    const float *d_positions, const float *d_flag, size_t flag_stride,
+                                    float *d_lm_out, zr_view_desc *d_views, void *hip_stream);
 /* The sampling parameters the preprocessing derives from each zr_view: glibc cosf/sinf of the
  * angle (rect.rs:135-137,417-423), so a caller can build or check a device view table.  A view
  * whose frame index is past the call's frame table samples Color::NONE everywhere. */
@@ -387,6 +433,7 @@ int zr_free(void *p);
 int zr_host_alloc(void **p, size_t bytes); /* page-locked host memory (truly async copies) */
 int zr_host_free(void *p);
 int zr_memcpy_async(void *dst, const void *src, size_t bytes, int kind, void *hip_stream);
+int zr_memset_async(void *dst, int value, size_t bytes, void *hip_stream); /* every byte = value */
 /* height rows of width bytes, row pitches dpitch / spitch */
 int zr_memcpy2d_async(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height,
                       int kind, void *hip_stream);

@@ -35,6 +35,40 @@ class Frame(C.Structure):
                 ("row_stride", C.c_uint64)]
 
 
+class TrackState(C.Structure):
+    """zr_track_state: one tracked ROI in HBM."""
+    _fields_ = [("roi", C.c_float * 5), ("view_rect", C.c_float * 5), ("local", C.c_float * 3),
+                ("active", C.c_uint32), ("frame_w", C.c_uint32), ("frame_h", C.c_uint32),
+                ("tracked", C.c_uint32), ("confidence", C.c_float), ("updated", C.c_float * 5)]
+
+
+class TrackCfg(C.Structure):
+    """zr_track_cfg."""
+    _fields_ = [("kind", C.c_int), ("num_landmarks", C.c_int), ("in_w", C.c_int), ("in_h", C.c_int),
+                ("aspect_w", C.c_int), ("aspect_h", C.c_int), ("loss_thresh", C.c_float),
+                ("padding", C.c_float), ("rois_per_frame", C.c_int)]
+
+
+class LmFilter(C.Structure):
+    """zr_lm_filter: kind 0 none, 1 EMA {alpha}, 2 alpha-beta {alpha, beta}, 3 1 euro
+    {min_cutoff, beta, d_cutoff}."""
+    _fields_ = [("kind", C.c_int), ("p", C.c_float * 3)]
+
+    @classmethod
+    def make(cls, kind: int, *p: float):
+        f = cls()
+        f.kind = kind
+        for i, v in enumerate(p):
+            f.p[i] = v
+        return f
+
+
+def lm_filter_state_size(f: LmFilter, num_landmarks: int) -> int:
+    n = C.c_size_t(0)
+    check(lib().zr_lm_filter_state_size(C.byref(f), num_landmarks, C.byref(n)))
+    return n.value
+
+
 _LIB = None
 
 # (name, restype, argtypes) for every exported entry point of include/zaru_hip.h
@@ -52,6 +86,9 @@ SIGNATURES = [
     ("zr_detection_candidates_async", _I, [_P, _P, _U32, _U32, _U32, _F, _U32, _P, _P, _P]),
     ("zr_track_seed_async", _I, [_P, _SZ, _P, _P, _P]),
     ("zr_track_update_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _P]),
+    ("zr_lm_filter_state_size", _I, [_P, _SZ, C.POINTER(_SZ)]),
+    ("zr_lm_filter_async", _I, [_P, _P, _P, _SZ, _P, _SZ, _P, _SZ, _F, _P, _P, _P]),
+    ("zr_track_update_positions_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P]),
     ("zr_view_describe", _I, [_P, _SZ, _U32, _P]),
     ("zr_detect_post_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _U32, _U32, _P, _P]),
     ("zr_detect_post_mapped_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _P]),
@@ -89,6 +126,7 @@ SIGNATURES = [
     ("zr_host_alloc", _I, [C.POINTER(_P), _SZ]),
     ("zr_host_free", _I, [_P]),
     ("zr_memcpy_async", _I, [_P, _P, _SZ, _I, _P]),
+    ("zr_memset_async", _I, [_P, _I, _SZ, _P]),
     ("zr_memcpy2d_async", _I, [_P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
     ("zr_stream_create", _I, [C.POINTER(_P)]),
     ("zr_stream_destroy", _I, [_P]),

@@ -66,6 +66,29 @@ LandmarkNetwork landmark_net(const std::string &name) {
                     "landmark network must be 'facemesh', 'facemesh_v2', 'hand', 'eye', 'face68_pfld' or 'face68_peppa'");
 }
 
+// set_filter's argument: None, Ema, AlphaBeta or OneEuro
+std::optional<FilterParams> filter_arg(const py::object &o) {
+    if (o.is_none()) return std::nullopt;
+    if (py::isinstance<Ema>(o)) return FilterParams(o.cast<Ema>());
+    if (py::isinstance<AlphaBeta>(o)) return FilterParams(o.cast<AlphaBeta>());
+    if (py::isinstance<OneEuro>(o)) return FilterParams(o.cast<OneEuro>());
+    throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "filter must be None, Ema, AlphaBeta or OneEuro");
+}
+
+std::vector<Image> device_frames(const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames) {
+    std::vector<Image> im;
+    for (auto &f : frames) {
+        Image i;
+        i.rgba = reinterpret_cast<const uint8_t *>(std::get<0>(f));
+        i.width = std::get<1>(f);
+        i.height = std::get<2>(f);
+        i.row_stride = std::get<3>(f);
+        i.on_device = true;
+        im.push_back(i);
+    }
+    return im;
+}
+
 // Detector::detect_impl after inference on raw outputs (detection.rs:231-267)
 std::vector<Detection> detect_post(const std::string &net, py::array_t<float, py::array::c_style> boxes,
                                    py::array_t<float, py::array::c_style> logits, uint32_t img_w,
@@ -240,18 +263,51 @@ PYBIND11_MODULE(_zaru_host, m) {
             return d.detect(host_image(img));
         });
 
+    // crates/zaru/src/filter: the parameters of the three landmark filters, and LandmarkFilter
+    // (landmark.rs:142-202) usable alone on (L, 3) float32 arrays
+    py::class_<Ema>(m, "Ema").def(py::init<float>(), py::arg("alpha")).def_readonly("alpha", &Ema::alpha);
+    py::class_<AlphaBeta>(m, "AlphaBeta")
+        .def(py::init<float, float>(), py::arg("alpha"), py::arg("beta"))
+        .def_readonly("alpha", &AlphaBeta::alpha)
+        .def_readonly("beta", &AlphaBeta::beta);
+    py::class_<OneEuro>(m, "OneEuro")
+        .def(py::init<float, float, float>(), py::arg("min_cutoff"), py::arg("beta"), py::arg("d_cutoff") = 1.f)
+        .def_readonly("min_cutoff", &OneEuro::min_cutoff)
+        .def_readonly("beta", &OneEuro::beta)
+        .def_readonly("d_cutoff", &OneEuro::d_cutoff);
+    py::class_<LandmarkFilter>(m, "LandmarkFilter")
+        .def(py::init([](const py::object &f, size_t n) {
+                 auto p = filter_arg(f);
+                 if (!p) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "filter must be Ema, AlphaBeta or OneEuro");
+                 return new LandmarkFilter(*p, n);
+             }), py::arg("filter"), py::arg("num_landmarks"))
+        .def("num_landmarks", &LandmarkFilter::num_landmarks)
+        .def("reset", &LandmarkFilter::reset)
+        .def("filter", [](LandmarkFilter &f, py::array_t<float, py::array::c_style | py::array::forcecast> pos,
+                          float elapsed) {
+            if (pos.ndim() != 2 || pos.shape(1) != 3) throw ZaruError(ZR_ERR_SHAPE, "positions must be (L, 3) float32");
+            py::array_t<float> out({pos.shape(0), (py::ssize_t)3});
+            std::memcpy(out.mutable_data(), pos.data(), (size_t)pos.size() * 4);
+            f.filter(out.mutable_data(), (size_t)pos.shape(0), elapsed);
+            return out;
+        }, py::arg("positions"), py::arg("elapsed") = Estimator::DEFAULT_FILTER_DT);
+
     py::class_<Estimator>(m, "Estimator")
         .def(py::init([](const std::string &net, int device) { return new Estimator(landmark_net(net), device); }),
              py::arg("network") = "facemesh", py::arg("device") = 0)
         .def("input_width", &Estimator::input_width)
-        .def("estimate", [](Estimator &e, py::array_t<uint8_t, py::array::c_style> img, const ViewData &v) {
+        .def("set_filter", [](Estimator &e, const py::object &f, float dt) { e.set_filter(filter_arg(f), dt); },
+             py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
+        .def("estimate", [](Estimator &e, py::array_t<uint8_t, py::array::c_style> img, const ViewData &v,
+                            std::optional<float> elapsed) {
             Image im = host_image(img);
-            return estimate_dict(e.estimate(im, v));
-        })
-        .def("estimate_image", [](Estimator &e, py::array_t<uint8_t, py::array::c_style> img) {
+            return estimate_dict(e.estimate(im, v, elapsed));
+        }, py::arg("image"), py::arg("view"), py::arg("elapsed") = py::none())
+        .def("estimate_image", [](Estimator &e, py::array_t<uint8_t, py::array::c_style> img,
+                                  std::optional<float> elapsed) {
             Image im = host_image(img);
-            return estimate_dict(e.estimate(im, ViewData::full(im.width, im.height)));
-        })
+            return estimate_dict(e.estimate(im, ViewData::full(im.width, im.height), elapsed));
+        }, py::arg("image"), py::arg("elapsed") = py::none())
         .def("angle_radians", [](const Estimator &e, py::array_t<float, py::array::c_style> lm) {
             Estimate est;
             est.positions.assign(lm.data(), lm.data() + lm.size());
@@ -270,14 +326,17 @@ PYBIND11_MODULE(_zaru_host, m) {
             if (!t.roi()) return py::none();
             return py::cast(*t.roi());
         })
-        .def("track", [](LandmarkTracker &t, py::array_t<uint8_t, py::array::c_style> img) -> py::object {
-            auto r = t.track(host_image(img));
+        .def("set_filter", [](LandmarkTracker &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
+             py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
+        .def("track", [](LandmarkTracker &t, py::array_t<uint8_t, py::array::c_style> img,
+                         std::optional<float> elapsed) -> py::object {
+            auto r = t.track(host_image(img), elapsed);
             if (!r) return py::none();
             py::dict d = estimate_dict(r->estimate);
             d["view_rect"] = r->view_rect;
             d["updated_roi"] = r->updated_roi;
             return d;
-        });
+        }, py::arg("image"), py::arg("elapsed") = py::none());
 
     py::class_<HandTracker>(m, "HandTracker")
         .def(py::init<int>(), py::arg("device") = 0)
@@ -363,20 +422,14 @@ PYBIND11_MODULE(_zaru_host, m) {
                                std::get<4>(v));
             t.set_rois(r, sizes);
         })
-        .def("step", [](DeviceTracker &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames) {
-            std::vector<Image> im;
-            for (auto &f : frames) {
-                Image i;
-                i.rgba = reinterpret_cast<const uint8_t *>(std::get<0>(f));
-                i.width = std::get<1>(f);
-                i.height = std::get<2>(f);
-                i.row_stride = std::get<3>(f);
-                i.on_device = true;
-                im.push_back(i);
-            }
+        .def("step", [](DeviceTracker &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
+                        std::optional<float> elapsed) {
+            const std::vector<Image> im = device_frames(frames);
             py::gil_scoped_release nogil;
-            t.step(im);
-        })
+            t.step(im, elapsed);
+        }, py::arg("frames"), py::arg("elapsed") = py::none())
+        .def("set_filter", [](DeviceTracker &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
+             py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
         .def("synchronize", &DeviceTracker::synchronize, py::call_guard<py::gil_scoped_release>())
         .def("__len__", &DeviceTracker::size)
         .def("states", [](DeviceTracker &t) {
@@ -424,20 +477,14 @@ PYBIND11_MODULE(_zaru_host, m) {
              py::arg("loss_threshold") = LandmarkTracker::DEFAULT_LOSS_THRESHOLD,
              py::arg("det_threshold") = Detector::DEFAULT_THRESHOLD)
         .def("set_roi", &DeviceFaceLoop::set_roi)
-        .def("step", [](DeviceFaceLoop &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames) {
-            std::vector<Image> im;
-            for (auto &f : frames) {
-                Image i;
-                i.rgba = reinterpret_cast<const uint8_t *>(std::get<0>(f));
-                i.width = std::get<1>(f);
-                i.height = std::get<2>(f);
-                i.row_stride = std::get<3>(f);
-                i.on_device = true;
-                im.push_back(i);
-            }
+        .def("step", [](DeviceFaceLoop &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
+                        std::optional<float> elapsed) {
+            const std::vector<Image> im = device_frames(frames);
             py::gil_scoped_release nogil;
-            t.step(im);
-        })
+            t.step(im, elapsed);
+        }, py::arg("frames"), py::arg("elapsed") = py::none())
+        .def("set_filter", [](DeviceFaceLoop &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
+             py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
         .def("synchronize", &DeviceFaceLoop::synchronize, py::call_guard<py::gil_scoped_release>())
         .def("__len__", &DeviceFaceLoop::streams)
         .def("states", [](DeviceFaceLoop &t) {

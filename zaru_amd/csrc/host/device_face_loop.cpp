@@ -105,8 +105,13 @@ void DeviceFaceLoop::frame_size(uint32_t W, uint32_t H) {
     check(zr_stream_synchronize(stream_));
 }
 
-void DeviceFaceLoop::step(const std::vector<Image> &frames) {
+void DeviceFaceLoop::set_filter(const std::optional<FilterParams> &f, float dt) {
+    filter_.set(f, dt, (size_t)lm_net_.num_landmarks, n_, stream_);
+}
+
+void DeviceFaceLoop::step(const std::vector<Image> &frames, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
+    const float el = filter_.on() ? filter_.elapsed(elapsed) : 0.f;  // checked before anything is enqueued
     std::vector<zr_frame> zf(n_);
     for (size_t i = 0; i < n_; i++) {
         const Image &f = frames[i];
@@ -150,8 +155,17 @@ void DeviceFaceLoop::step(const std::vector<Image> &frames) {
     float *louts[4] = {lm_outs_[0].ptr, lm_outs_[1].ptr, lm_outs_[2].ptr, lm_outs_[3].ptr};
     const ColorMapper lc = lm_->color_mapper();
     check(zr_cnn_estimate_device_views_async(ln.handle(), zf.data(), n_, views_.ptr, n_, lc.lo, lc.hi, louts, stream_));
-    check(zr_track_update_async(state_.ptr, n_, &tcfg_, lm_outs_[0].ptr, (size_t)ln.output_per_image(0),
-                                lm_outs_[1].ptr, (size_t)ln.output_per_image(1), lm_out_.ptr, views_.ptr, stream_));
+    if (filter_.on()) {  // Estimator's filter between extract and map-out (landmark.rs:330-333)
+        check(zr_lm_filter_async(&filter_.f, &tcfg_, state_.ptr, n_, lm_outs_[0].ptr, (size_t)ln.output_per_image(0),
+                                 lm_outs_[1].ptr, (size_t)ln.output_per_image(1), el, filter_.state.ptr,
+                                 filter_.pos.ptr, stream_));
+        check(zr_track_update_positions_async(state_.ptr, n_, &tcfg_, filter_.pos.ptr, lm_outs_[1].ptr,
+                                              (size_t)ln.output_per_image(1), lm_out_.ptr, views_.ptr, stream_));
+    } else {
+        check(zr_track_update_async(state_.ptr, n_, &tcfg_, lm_outs_[0].ptr, (size_t)ln.output_per_image(0),
+                                    lm_outs_[1].ptr, (size_t)ln.output_per_image(1), lm_out_.ptr, views_.ptr,
+                                    stream_));
+    }
     // 3-4: detector.detect on the streams whose track returned None (facemesh.rs:43-47)
     check(zr_track_lost_compact_async(state_.ptr, n_, &det_tmpl_, due_.ptr, ndue_.ptr, due_views_.ptr,
                                       due_total_.ptr, stream_));

@@ -15,12 +15,15 @@
 //   5. the re-seeding of those streams from their most confident detection
 //      (zr_track_reseed_best_async), which writes the view the next frame's estimate samples.
 // A stream with no RoI at construction detects on its first frame, as the demo starts.
+// With a landmark filter set (set_filter), step 2 is zr_lm_filter_async followed by
+// zr_track_update_positions_async: the RoI follows the filtered landmarks.
 #pragma once
 #include <memory>
 #include <utility>
 #include <vector>
 
 #include "detection.h"
+#include "device_tracker.h"
 #include "landmark.h"
 
 namespace zh {
@@ -38,7 +41,13 @@ class DeviceFaceLoop {
     // LandmarkTracker::set_roi for stream s before its next frame (test / warm-start hook)
     void set_roi(size_t s, const RotatedRect &roi);
     // one device-resident frame per stream (all of one size); enqueue only
-    void step(const std::vector<Image> &frames);
+    // with a filter set: `elapsed` seconds since the previous step, one value for all streams
+    // (default: the filter's dt)
+    void step(const std::vector<Image> &frames, std::optional<float> elapsed = std::nullopt);
+    // Estimator::set_filter for every stream's tracker (nullopt: none): replaces the filter and
+    // resets its state.  set_roi, tracking loss and the re-seeding leave the state alone, as the
+    // reference does; an inactive stream runs no estimate, so its state waits unchanged.
+    void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
     void synchronize();
     size_t streams() const { return n_; }
     const LandmarkNetwork &landmarker() const { return lm_net_; }
@@ -69,6 +78,7 @@ class DeviceFaceLoop {
     DeviceArray<uint32_t> fsize_;
     DeviceArray<int32_t> due_, ndue_, count_;
     DeviceArray<uint64_t> due_total_, reseeded_;
+    DeviceFilter filter_;
 };
 
 }  // namespace zh

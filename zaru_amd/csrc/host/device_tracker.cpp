@@ -11,6 +11,41 @@ int track_kind(NetworkKind k) {
     throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "not a landmark network");
 }
 
+void DeviceFilter::set(const std::optional<FilterParams> &p, float dt_s, size_t num_landmarks, size_t n,
+                       void *stream) {
+    if (!p) {
+        f = zr_lm_filter{};
+        dt = dt_s;
+        return;
+    }
+    check_filter_params(*p);
+    check_elapsed(*p, dt_s);
+    size_t b = 0;
+    check(zr_lm_filter_state_size(&p->f, num_landmarks, &b));
+    f = p->f;
+    dt = dt_s;
+    bytes = b;
+    reset(num_landmarks, n, stream);
+}
+
+void DeviceFilter::reset(size_t num_landmarks, size_t n, void *stream) {
+    streams = n;
+    if (!on() || n == 0) return;
+    // a grown array is a new allocation: nothing enqueued may still use the old one
+    if (bytes * n > state.n || n * num_landmarks * 3 > pos.n) check(zr_stream_synchronize(stream));
+    state.resize(bytes * n);
+    pos.resize(n * num_landmarks * 3);
+    check(zr_memset_async(state.ptr, 0, bytes * n, stream));  // all-zero: no value seen
+}
+
+float DeviceFilter::elapsed(const std::optional<float> &e) const {
+    const float el = e.value_or(dt);
+    FilterParams p;
+    p.f = f;
+    check_elapsed(p, el);
+    return el;
+}
+
 DeviceTracker::DeviceTracker(LandmarkNetwork net, int device, float padding, float loss_thresh)
     : net_(net), cnn_(network_cnn(net.kind, device)) {
     if (!(padding >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "roi padding must be >= 0");
@@ -57,13 +92,21 @@ void DeviceTracker::set_rois(const std::vector<RotatedRect> &rois,
     const NeuralNetwork &nn = cnn_->nn();
     for (size_t k = 0; k < nn.num_outputs() && k < 4; k++) outs_[k].resize((size_t)nn.output_per_image(k) * n_);
     lm_out_.resize(n_ * (size_t)net_.num_landmarks * 3);
+    // set_roi keeps the filter state (landmark.rs:293-302 resets it only in set_filter); a new
+    // stream count starts new streams
+    if (filter_.streams != n_) filter_.reset((size_t)net_.num_landmarks, n_, stream_);
     check(zr_memcpy_async(state_.ptr, h.data(), n_ * sizeof(zr_track_state), 0, stream_));
     check(zr_track_seed_async(state_.ptr, n_, &cfg_, views_.ptr, stream_));
     check(zr_stream_synchronize(stream_));  // `h` is pageable and goes out of scope
 }
 
-void DeviceTracker::step(const std::vector<Image> &frames) {
+void DeviceTracker::set_filter(const std::optional<FilterParams> &f, float dt) {
+    filter_.set(f, dt, (size_t)net_.num_landmarks, n_, stream_);
+}
+
+void DeviceTracker::step(const std::vector<Image> &frames, std::optional<float> elapsed) {
     if (frames.size() != n_ || n_ == 0) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per tracked ROI");
+    const float el = filter_.on() ? filter_.elapsed(elapsed) : 0.f;  // checked before anything is enqueued
     std::vector<zr_frame> zf(n_);
     for (size_t i = 0; i < n_; i++) {
         if (!frames[i].on_device) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "tracker frames must be device-resident");
@@ -75,6 +118,16 @@ void DeviceTracker::step(const std::vector<Image> &frames) {
     // the frame table is staged (pinned) inside the call, so zf may die after it returns
     check(zr_cnn_estimate_device_views_async(nn.handle(), zf.data(), n_, views_.ptr, n_, cm.lo, cm.hi, outs, stream_));
     const bool flagged = cfg_.kind <= 2;  // flag output, or (kind 2) the iris output
+    if (filter_.on()) {  // extract + filter, then the update on the filtered positions
+        check(zr_lm_filter_async(&filter_.f, &cfg_, state_.ptr, n_, outs_[0].ptr, (size_t)nn.output_per_image(0),
+                                 flagged ? outs_[1].ptr : nullptr, flagged ? (size_t)nn.output_per_image(1) : 0, el,
+                                 filter_.state.ptr, filter_.pos.ptr, stream_));
+        check(zr_track_update_positions_async(state_.ptr, n_, &cfg_, filter_.pos.ptr,
+                                              flagged ? outs_[1].ptr : nullptr,
+                                              flagged ? (size_t)nn.output_per_image(1) : 0, lm_out_.ptr, views_.ptr,
+                                              stream_));
+        return;
+    }
     check(zr_track_update_async(state_.ptr, n_, &cfg_, outs_[0].ptr, (size_t)nn.output_per_image(0),
                                 flagged ? outs_[1].ptr : nullptr, flagged ? (size_t)nn.output_per_image(1) : 0,
                                 lm_out_.ptr, views_.ptr, stream_));

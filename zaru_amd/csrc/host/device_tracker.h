@@ -14,6 +14,27 @@ namespace zh {
 // the track kernel's extract / angle kind of a landmark network (zr_track_cfg::kind)
 int track_kind(NetworkKind k);
 
+// A device loop's landmark filter (Estimator::set_filter, landmark.rs:293-302): the parameters,
+// the per-stream filter state in HBM (kernels/lm_filter.hip) and the filtered positions the
+// update consumes.  With a filter set a step enqueues, on the loop's stream,
+//     network -> zr_lm_filter_async -> zr_track_update_positions_async
+// instead of network -> zr_track_update_async; without one nothing changes.
+struct DeviceFilter {
+    zr_lm_filter f{};  // kind ZR_LM_FILTER_NONE: no filter
+    float dt = Estimator::DEFAULT_FILTER_DT;
+    size_t bytes = 0;    // filter state per stream
+    size_t streams = 0;  // the stream count the state holds
+    DeviceArray<uint8_t> state;
+    DeviceArray<float> pos;
+    bool on() const { return f.kind != ZR_LM_FILTER_NONE; }
+    // replace the filter; `streams` (may be 0: sized later) default states, zeroed on `stream`
+    void set(const std::optional<FilterParams> &p, float dt, size_t num_landmarks, size_t streams, void *stream);
+    // (re)size for `streams` and reset every state
+    void reset(size_t num_landmarks, size_t streams, void *stream);
+    // the elapsed time of a step: the call's, or the filter's dt; checked for the time-based kinds
+    float elapsed(const std::optional<float> &e) const;
+};
+
 class DeviceTracker {
   public:
     DeviceTracker(LandmarkNetwork net, int device = 0, float padding = LandmarkTracker::DEFAULT_ROI_PADDING,
@@ -25,7 +46,12 @@ class DeviceTracker {
     // LandmarkTracker::set_roi for every stream, with each stream's frame size
     void set_rois(const std::vector<RotatedRect> &rois, const std::vector<std::pair<uint32_t, uint32_t>> &sizes);
     // one device-resident frame per stream (frames[i] -> ROI i): estimate + update, enqueue only
-    void step(const std::vector<Image> &frames);
+    // with a filter set: `elapsed` seconds since the previous step, one value for all streams
+    // (default: the filter's dt)
+    void step(const std::vector<Image> &frames, std::optional<float> elapsed = std::nullopt);
+    // Estimator::set_filter for every stream (nullopt: none): replaces the filter and resets its
+    // state.  set_rois leaves the filter state alone while the stream count stays the same.
+    void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
     void synchronize();
     size_t size() const { return n_; }
     const LandmarkNetwork &network() const { return net_; }
@@ -45,6 +71,7 @@ class DeviceTracker {
     DeviceArray<zr_track_state> state_;
     DeviceArray<zr_view_desc> views_;
     DeviceArray<float> outs_[4], lm_out_;
+    DeviceFilter filter_;
 };
 
 }  // namespace zh

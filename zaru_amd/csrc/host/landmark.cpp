@@ -74,14 +74,28 @@ ViewData Estimator::network_view(const ViewData &view, Rect *rect_out) const {
     return view.view(RotatedRect(rect, 0.f));
 }
 
-Estimate &Estimator::estimate(const Image &img, const ViewData &view) {
+void Estimator::set_filter(const std::optional<FilterParams> &f, float dt) {
+    if (f) {
+        check_filter_params(*f);
+        check_elapsed(*f, dt);
+        filter_.emplace(*f, (size_t)net_.num_landmarks);
+    } else {
+        filter_.reset();
+    }
+    dt_ = dt;
+}
+
+Estimate &Estimator::estimate(const Image &img, const ViewData &view, std::optional<float> elapsed) {
+    const float el = elapsed.value_or(dt_);
+    if (filter_) check_elapsed(filter_->params(), el);  // before the network runs
     Rect rect;
     const ViewData v = network_view(view, &rect);
     auto outs = cnn_->estimate(img, {v});
     std::vector<const float *> ptrs;
     for (auto &o : outs) ptrs.push_back(o.data());
     extract_landmarks(net_, ptrs.data(), est_, cnn_->input_width(), cnn_->input_height());
-    // the default LandmarkFilter is a no-op (landmark.rs:151-158)
+    // landmark.rs:330-333; the default LandmarkFilter is a no-op (landmark.rs:151-158)
+    if (filter_) filter_->filter(est_.positions.data(), est_.size(), el);
     map_estimate(est_, rect, cnn_->input_width());
     return est_;
 }
@@ -113,12 +127,12 @@ void LandmarkTracker::set_roi_padding(float p) {
     pad_ = p;
 }
 
-std::optional<TrackingResult> LandmarkTracker::track(const Image &full) {
+std::optional<TrackingResult> LandmarkTracker::track(const Image &full, std::optional<float> elapsed) {
     if (!roi_) return std::nullopt;
     const RotatedRect roi = *roi_;
     const RotatedRect view_rect = roi.grow_to_fit_aspect(est_.aspect());
     const ViewData view = ViewData::full(full.width, full.height).view(view_rect);
-    Estimate &e = est_.estimate(full, view);
+    Estimate &e = est_.estimate(full, view, elapsed);
     TrackingResult res;
     RotatedRect next;
     if (!tracker_update(est_.network(), roi, view_rect, loss_, pad_, e, res, next)) {

@@ -6,6 +6,7 @@
 #include <optional>
 #include <vector>
 
+#include "filter.h"
 #include "geometry.h"
 #include "networks.h"
 
@@ -57,8 +58,14 @@ class Estimator {  // landmark.rs:256-349
     const Cnn &cnn() const { return *cnn_; }
     uint32_t input_width() const { return cnn_->input_width(); }
     AspectRatio aspect() const { return cnn_->aspect(); }
-    // estimate on a view of a host image; landmarks in the view's coordinates
-    Estimate &estimate(const Image &img, const ViewData &view);
+    static constexpr float DEFAULT_FILTER_DT = 1.f / 30.f;
+    // Estimator::set_filter (landmark.rs:293-302): replaces the filter and resets its state;
+    // nullopt is the default no-op filter.  `dt` is the elapsed time a filtered estimate uses
+    // when the call gives none (a frame interval, seconds).
+    void set_filter(const std::optional<FilterParams> &f, float dt = DEFAULT_FILTER_DT);
+    // estimate on a view of a host image; landmarks in the view's coordinates.  With a filter
+    // set, `elapsed` (seconds since the previous estimate, default: the filter's dt) drives it.
+    Estimate &estimate(const Image &img, const ViewData &view, std::optional<float> elapsed = std::nullopt);
     // the view actually sampled and the rect used for map-out (landmark.rs:320-323)
     ViewData network_view(const ViewData &view, Rect *rect_out) const;
 
@@ -66,6 +73,8 @@ class Estimator {  // landmark.rs:256-349
     LandmarkNetwork net_;
     std::shared_ptr<const Cnn> cnn_;
     Estimate est_;
+    std::optional<LandmarkFilter> filter_;
+    float dt_ = DEFAULT_FILTER_DT;
 };
 
 struct TrackingResult {  // landmark.rs:504-529
@@ -92,8 +101,13 @@ class LandmarkTracker {  // landmark.rs:361-502
     Estimator &estimator() { return est_; }
     float loss_threshold() const { return loss_; }
     float roi_padding() const { return pad_; }
-    // nullopt when no ROI is set or tracking was lost
-    std::optional<TrackingResult> track(const Image &full);
+    // Estimator::set_filter; the filter state is kept across set_roi and tracking loss
+    void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT) {
+        est_.set_filter(f, dt);
+    }
+    // nullopt when no ROI is set (no estimate runs: the filter state is untouched) or tracking
+    // was lost (the estimate ran and updated it); `elapsed`: seconds since the previous frame
+    std::optional<TrackingResult> track(const Image &full, std::optional<float> elapsed = std::nullopt);
 
   private:
     Estimator est_;

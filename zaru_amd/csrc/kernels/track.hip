@@ -96,11 +96,17 @@ __global__ __launch_bounds__(256) void track_kernel(const TrackParams P) {
         // L x 3, 2L for kind 3, or the 71-point eye contour for kind 2, whose 5 iris points come
         // first from output 1, eye.rs:47-64)
         const float *lm = P.lm + (int64_t)i * P.lm_stride;
-        const float *iris = P.kind == 2 ? P.flag + (int64_t)i * P.flag_stride : nullptr;
+        const float *iris = P.kind == 2 && !P.pos ? P.flag + (int64_t)i * P.flag_stride : nullptr;
+        // already extracted (and filtered, lm_filter.hip) positions of this ROI, when given
+        const float *pos = P.pos ? P.pos + (int64_t)i * L * 3 : nullptr;
         const float scale = st.local[2] / (float)P.in_w;
         // map-out of landmark j (Estimator, landmark.rs:336-345): p * scale, then + rect.x / .y
         auto mapped = [&](int j, float &x, float &y, float &z) {
-            if (P.kind == 3) {  // multipie68.rs:71-80: relative (x, y) * input resolution, z = 0
+            if (pos) {
+                x = pos[3 * j];
+                y = pos[3 * j + 1];
+                z = pos[3 * j + 2];
+            } else if (P.kind == 3) {  // multipie68.rs:71-80: relative (x, y) * input resolution, z = 0
                 x = lm[2 * j] * (float)P.in_w;
                 y = lm[2 * j + 1] * (float)P.in_h;
                 z = 0.f;

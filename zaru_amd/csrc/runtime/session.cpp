@@ -612,14 +612,36 @@ int zr_cnn_estimate_views_async(zr_session *s, const zr_frame *frames, size_t n_
 static_assert(sizeof(zr_track_state) == sizeof(zr::TrackState), "zr_track_state layout");
 static_assert(sizeof(zr_view_desc) == sizeof(zr::ViewDesc), "zr_view_desc layout");
 
-static int track_params(zr::TrackParams &p, zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
-                        zr_view_desc *d_views) {
-    if (!d_state || !cfg || !d_views || n == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument or n == 0");
+static int check_track_cfg(const zr_track_cfg *cfg, size_t n) {
+    if (!cfg || n == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument or n == 0");
     if (cfg->kind < 0 || cfg->kind > 3 || cfg->num_landmarks <= 0 || cfg->in_w <= 0 || cfg->in_h <= 0 ||
         cfg->aspect_w <= 0 || cfg->aspect_h <= 0 || !(cfg->padding >= 0.f) || n > (1u << 24))
         return set_err(ZR_ERR_INVALID_ARGUMENT, "bad tracker configuration");
     if ((cfg->kind == 0 && cfg->num_landmarks <= 263) || (cfg->kind == 1 && cfg->num_landmarks <= 9))
         return set_err(ZR_ERR_INVALID_ARGUMENT, "angle landmarks out of range");
+    return ZR_OK;
+}
+
+// what each kind's extract reads of the raw outputs (mediapipe.rs:59-71, hand/landmark.rs:298-322,
+// eye.rs:47-64, multipie68.rs:71,108: outputs[0][..NUM_LANDMARKS * 2])
+static int check_extract_inputs(const zr_track_cfg *cfg, const float *d_landmarks, size_t lm_stride,
+                                const float *d_flag, size_t flag_stride) {
+    if (!d_landmarks || (cfg->kind <= 2 && (!d_flag || flag_stride == 0)))
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "missing landmark / flag outputs");
+    if (flag_stride > (size_t)INT32_MAX) return set_err(ZR_ERR_INVALID_ARGUMENT, "flag stride too large");
+    if (cfg->kind == 2 && (cfg->num_landmarks <= 5 || flag_stride < 15))
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "eye network: output 1 holds the 5 iris points");
+    const size_t L = (size_t)cfg->num_landmarks;
+    const size_t need = cfg->kind == 3 ? 2 * L : cfg->kind == 2 ? 3 * (L - 5) : 3 * L;
+    if (lm_stride < need || lm_stride > (size_t)INT32_MAX)
+        return set_err(ZR_ERR_SHAPE, "landmark output holds fewer floats per image than the extract reads");
+    return ZR_OK;
+}
+
+static int track_params(zr::TrackParams &p, zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                        zr_view_desc *d_views) {
+    if (!d_state || !cfg || !d_views || n == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument or n == 0");
+    if (int rc = check_track_cfg(cfg, n)) return rc;
     p.state = reinterpret_cast<zr::TrackState *>(d_state);
     p.views = reinterpret_cast<zr::ViewDesc *>(d_views);
     p.n = (int)n;
@@ -654,22 +676,107 @@ int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg 
     return guarded([&]() -> int {
         zr::TrackParams p{};
         if (int rc = track_params(p, d_state, n, cfg, d_views)) return rc;
-        if (!d_landmarks || (cfg->kind <= 2 && (!d_flag || flag_stride == 0)))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "missing landmark / flag outputs");
-        if (cfg->kind == 2 && (cfg->num_landmarks <= 5 || flag_stride < 15))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "eye network: output 1 holds the 5 iris points");
-        // what each kind's extract reads of output 0 (mediapipe.rs:59-71, hand/landmark.rs:298-322,
-        // eye.rs:47-64, multipie68.rs:71,108: outputs[0][..NUM_LANDMARKS * 2])
-        const size_t L = (size_t)cfg->num_landmarks;
-        const size_t need = cfg->kind == 3 ? 2 * L : cfg->kind == 2 ? 3 * (L - 5) : 3 * L;
-        if (lm_stride < need || lm_stride > (size_t)INT32_MAX)
-            return set_err(ZR_ERR_SHAPE, "landmark output holds fewer floats per image than the extract reads");
+        if (int rc = check_extract_inputs(cfg, d_landmarks, lm_stride, d_flag, flag_stride)) return rc;
         p.lm = d_landmarks;
         p.lm_stride = (int)lm_stride;
         p.flag = d_flag;
         p.flag_stride = (int)flag_stride;
         p.lm_out = d_lm_out;
         zr::launch_track(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                    const float *d_positions, const float *d_flag, size_t flag_stride,
+                                    float *d_lm_out, zr_view_desc *d_views, void *hip_stream) {
+    return guarded([&]() -> int {
+        zr::TrackParams p{};
+        if (int rc = track_params(p, d_state, n, cfg, d_views)) return rc;
+        if (!d_positions) return set_err(ZR_ERR_INVALID_ARGUMENT, "missing positions");
+        if (cfg->kind <= 1 && (!d_flag || flag_stride == 0 || flag_stride > (size_t)INT32_MAX))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "missing flag output");
+        p.pos = d_positions;
+        if (cfg->kind <= 1) {  // the confidence; kinds 2/3 have none, and the iris points are in d_positions
+            p.flag = d_flag;
+            p.flag_stride = (int)flag_stride;
+        }
+        p.lm_out = d_lm_out;
+        zr::launch_track(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+// ---- landmark temporal filters (kernels/lm_filter.hip)
+static bool unit_interval(float v) { return v >= 0.f && v <= 1.f; }  // false for NaN
+
+static int check_lm_filter(const zr_lm_filter *f) {
+    if (!f) return set_err(ZR_ERR_INVALID_ARGUMENT, "null filter");
+    switch (f->kind) {
+        case ZR_LM_FILTER_NONE: return ZR_OK;
+        case ZR_LM_FILTER_EMA:
+            if (!unit_interval(f->p[0])) return set_err(ZR_ERR_INVALID_ARGUMENT, "Ema: alpha must be in [0, 1]");
+            return ZR_OK;
+        case ZR_LM_FILTER_ALPHA_BETA:
+            if (!unit_interval(f->p[0]) || !unit_interval(f->p[1]))
+                return set_err(ZR_ERR_INVALID_ARGUMENT, "AlphaBeta: alpha and beta must be in [0, 1]");
+            return ZR_OK;
+        case ZR_LM_FILTER_ONE_EURO:
+            if (!(f->p[0] > 0.f) || !(f->p[1] >= 0.f))
+                return set_err(ZR_ERR_INVALID_ARGUMENT, "OneEuro: min_cutoff must be > 0 and beta >= 0");
+            return ZR_OK;
+        default: return set_err(ZR_ERR_INVALID_ARGUMENT, "unknown landmark filter kind");
+    }
+}
+
+int zr_lm_filter_state_size(const zr_lm_filter *filter, size_t num_landmarks, size_t *bytes) {
+    return guarded([&]() -> int {
+        if (!bytes) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_lm_filter(filter)) return rc;
+        if (num_landmarks == 0 || num_landmarks > (1u << 20))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "bad landmark count");
+        *bytes = zr::lm_filter_words(filter->kind, num_landmarks) * sizeof(uint32_t);
+        return ZR_OK;
+    });
+}
+
+int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, const zr_track_state *d_state,
+                       size_t n, const float *d_landmarks, size_t lm_stride, const float *d_flag,
+                       size_t flag_stride, float elapsed_s, void *d_filter_state, float *d_positions,
+                       void *hip_stream) {
+    return guarded([&]() -> int {
+        if (int rc = check_lm_filter(filter)) return rc;
+        if (int rc = check_track_cfg(cfg, n)) return rc;
+        if (int rc = check_extract_inputs(cfg, d_landmarks, lm_stride, d_flag, flag_stride)) return rc;
+        if (!d_positions || (filter->kind != ZR_LM_FILTER_NONE && !d_filter_state))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "missing positions / filter state");
+        // the time-based filters divide by it: a bad value would poison the state for good
+        if (filter->kind >= ZR_LM_FILTER_ALPHA_BETA && !(std::isfinite(elapsed_s) && elapsed_s > 0.f))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "a time-based filter needs a finite elapsed time > 0");
+        const uint64_t chunks = (3 * (uint64_t)cfg->num_landmarks + 255) / 256;
+        if (cfg->num_landmarks > (1 << 20) || n * chunks > (uint64_t)INT32_MAX)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "too many values for one launch");
+        zr::LmFilterParams p{};
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.lm = d_landmarks;
+        p.flag = d_flag;
+        p.pos = d_positions;
+        p.fstate = static_cast<uint32_t *>(d_filter_state);
+        p.n = (int)n;
+        p.L = cfg->num_landmarks;
+        p.lm_stride = (int)lm_stride;
+        p.flag_stride = (int)flag_stride;
+        p.kind = cfg->kind;
+        p.in_w = cfg->in_w;
+        p.in_h = cfg->in_h;
+        p.filter = filter->kind;
+        p.p0 = filter->p[0];
+        p.p1 = filter->p[1];
+        p.p2 = filter->p[2];
+        p.elapsed = elapsed_s;
+        zr::launch_lm_filter(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
@@ -1118,6 +1225,15 @@ int zr_memcpy_async(void *dst, const void *src, size_t bytes, int kind, void *hi
         hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost
                                                                         : hipMemcpyDeviceToDevice;
         HIP_TRY(hipMemcpyAsync(dst, src, bytes, k, (hipStream_t)hip_stream));
+        return ZR_OK;
+    });
+}
+
+int zr_memset_async(void *dst, int value, size_t bytes, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (bytes == 0) return ZR_OK;
+        if (!dst) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        HIP_TRY(hipMemsetAsync(dst, value, bytes, (hipStream_t)hip_stream));
         return ZR_OK;
     });
 }

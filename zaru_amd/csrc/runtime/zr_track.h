@@ -37,9 +37,32 @@ struct TrackParams {
     float loss_thresh, padding;
     int seed;              // 1: only derive views from state.roi (no estimate to consume)
     int rpf;               // ROIs per frame: ROI i samples frame i / rpf
+    const float *pos;      // null, or the already extracted positions (n x L x 3, network px:
+                           // lm_filter.hip) the map-out reads instead of extracting from lm / flag
 };
 
 const char *launch_track(const TrackParams &p, hipStream_t s);
+
+// Landmark temporal filter (kernels/lm_filter.hip): each stream's extract, then one filter per
+// landmark and coordinate (crates/zaru/src/filter; landmark.rs:142-202).
+struct LmFilterParams {
+    const TrackState *state;  // null: every stream is active
+    const float *lm, *flag;   // as TrackParams
+    float *pos;               // out: n x L x 3 network px (NaN rows: inactive streams)
+    uint32_t *fstate;         // n x lm_filter_words(kind, L) words (null for kind 0)
+    int n, L, lm_stride, flag_stride;
+    int kind;                 // the extract kind (TrackParams::kind)
+    int in_w, in_h;
+    int filter;               // 0 none, 1 EMA, 2 alpha-beta, 3 1 euro
+    float p0, p1, p2;         // the filter's parameters (zr_lm_filter::p)
+    float elapsed;
+};
+// 32-bit words of filter state per stream: structure of arrays over the 3L values -- primed
+// flags, then one (EMA) or two float arrays; all-zero is the default state
+inline size_t lm_filter_words(int filter, size_t L) {
+    return filter == 0 ? 0 : (filter == 1 ? 2 : 3) * 3 * L;
+}
+const char *launch_lm_filter(const LmFilterParams &p, hipStream_t s);
 
 // Detector::detect_impl after inference (detpost.hip): extract, weighted NMS, map to frame px.
 struct DetPostParams {
