@@ -2,6 +2,7 @@
 // folded into a GEMM epilogue): standalone activation / Add / MaxPool 2x2 / channel Pad,
 // bilinear Resize (half_pixel, palm FPN), GlobalAveragePool (hand head), plus the detector
 // candidate compaction that keeps the bit-exact decode on the host cheap.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -143,12 +144,13 @@ const char *launch_gap(const GapParams &p, hipStream_t s) {
 // plane) and accumulates them as gap_kernel does (s = 0 + v + ...), then gap_kernel's butterfly
 // and division.  Bitwise equal to dw_kernel -> gap_kernel.
 constexpr int DG_NB = 64;  // planes (images) per workgroup: one load latency for 64 planes
+constexpr int DG_LDS = 64 * 1024;  // the staged planes stay within the default dynamic-LDS limit
 
 template <int K>
-__global__ __launch_bounds__(256) void dwgap_kernel(const DwParams P, int S, int vec) {
-    extern __shared__ __attribute__((aligned(16))) float pl[];  // DG_NB planes of H * W
-    const int c = blockIdx.y, n0 = blockIdx.x * DG_NB;
-    const int nb = min(DG_NB, P.N - n0);
+__global__ __launch_bounds__(256) void dwgap_kernel(const DwParams P, int S, int vec, int NB) {
+    extern __shared__ __attribute__((aligned(16))) float pl[];  // NB planes of H * W
+    const int c = blockIdx.y, n0 = blockIdx.x * NB;
+    const int nb = min(NB, P.N - n0);
     const int H = P.in.H, W = P.in.W, HW = H * W, OHW = P.OH * P.OW;
     const float *src = P.in.p + (int64_t)c * P.in.sC + (int64_t)n0 * P.in.sN;
     if (vec) {  // the planes are contiguous (sN = H * W) and the run starts 16-B aligned
@@ -264,15 +266,18 @@ const char *launch_dwgap(const DwParams &p, hipStream_t s) {
             return "dwgap_lane_kernel<3,7,7,1,7,7,1,1>";
         }
     }
-    const dim3 grid((p.N + DG_NB - 1) / DG_NB, p.in.C);
-    const size_t lds = sizeof(float) * DG_NB * p.in.H * p.in.W;
+    // 64 planes of up to 256 floats; larger planes (the plan fuses up to 512) in fewer per workgroup,
+    // so the staging never asks for more than 64 KiB of LDS
     const int hw = p.in.H * p.in.W;
-    const int vec = p.in.sN == hw && p.in.sC % 4 == 0 && (DG_NB * hw) % 4 == 0 && (uintptr_t)p.in.p % 16 == 0;
+    const int nb = std::max(1, std::min(DG_NB, (int)(DG_LDS / sizeof(float)) / hw));
+    const dim3 grid((p.N + nb - 1) / nb, p.in.C);
+    const size_t lds = sizeof(float) * nb * hw;
+    const int vec = p.in.sN == hw && p.in.sC % 4 == 0 && (nb * hw) % 4 == 0 && (uintptr_t)p.in.p % 16 == 0;
     if (p.k == 3) {
-        hipLaunchKernelGGL((dwgap_kernel<3>), grid, dim3(256), lds, s, p, p.stride, vec);
+        hipLaunchKernelGGL((dwgap_kernel<3>), grid, dim3(256), lds, s, p, p.stride, vec, nb);
         return "dwgap_kernel<3>";
     }
-    hipLaunchKernelGGL((dwgap_kernel<5>), grid, dim3(256), lds, s, p, p.stride, vec);
+    hipLaunchKernelGGL((dwgap_kernel<5>), grid, dim3(256), lds, s, p, p.stride, vec, nb);
     return "dwgap_kernel<5>";
 }
 

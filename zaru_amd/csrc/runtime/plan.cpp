@@ -1031,12 +1031,13 @@ void Compiler::allocate() {
             if (!(last[o] < first[id] || last[id] < first[o]))
                 busy.push_back({P.storage_off[o], P.storage_off[o] + P.storage_size[o]});
         std::sort(busy.begin(), busy.end());
+        // (every candidate is 256-B aligned per image before the fit test: aligning the chosen
+        // offset afterwards could push a slot that fitted a hole into the next busy slot)
         int64_t off = 0;
         for (auto &b : busy) {
             if (off + P.storage_size[id] <= b.first) break;
-            off = std::max(off, b.second);
+            off = std::max(off, round_up(b.second, 64));
         }
-        off = round_up(off, 64);  // 256-B aligned slots per image
         P.storage_off[id] = off;
         arena = std::max(arena, off + P.storage_size[id]);
         placed.push_back(id);
@@ -1095,6 +1096,14 @@ bool Compiler::run(const std::vector<uint32_t> &sel) {
             if (s.out.kind == 2 && s.out.id == (int)oi) written = true;
         if (!written) return fail("output " + P.outputs[oi].name + " is never written");
     }
+    // Only the GEMM epilogues (S_GEMM, S_DWPW) carry a position stride: every other kernel stores
+    // positions with stride 1, so a folded NCHW->NHWC Transpose on its output would be written
+    // scrambled (inside the buffer, so nothing faults).  One position per image has no order.
+    for (auto &s : P.steps)
+        if (s.out.kind == 2 && s.out.o_sP != 1 && s.kind != S_GEMM && s.kind != S_DWPW &&
+            (int64_t)s.out.H * s.out.W > 1)
+            return fail("NHWC output on a non-GEMM step (" + s.name + "): only 1x1 / dense / depthwise->1x1 "
+                        "outputs can be transposed");
     for (auto &s : P.steps) {
         P.bytes_per_image += s.bytes;
         P.flops_per_image += s.flops;
