@@ -611,6 +611,19 @@ static bool valu_form(const DwPwParams &p) {
     return sizeof(float) * (size_t)VFKC * rows * (p.in.W + 8) <= 64 * 1024;
 }
 
+// launch_stem_dwpw's test: dwpw_valu_go's choice of dwpw_vres_kernel at stride 1
+bool dwpw_is_vres1(const DwPwParams &p) {
+    if (!valu_form(p) || p.stride != 1 || p.g.M > 32 || !form_on(FORM_VALU_DB)) return false;
+    const int P = p.g.P, tpi = (P + VTQ - 1) / VTQ;
+    int rmax = 0;
+    for (int t = 0; t < tpi; t++) {
+        const int q0 = t * VTQ, a = q0 / p.OW, b = std::min(q0 + VTQ - 1, P - 1) / p.OW;
+        rmax = std::max(rmax, b - a + p.k);
+    }
+    const size_t buf4 = (size_t)(4 * rmax * (p.in.W + 8) + 255) / 256 * 256;
+    return 2 * sizeof(float) * buf4 <= 64 * 1024 && vres_mode(p, 1, p.g.M <= 16 ? 16 : 32) == 1;
+}
+
 // High-resolution planes with few channels take the VALU form; the rest an MFMA form
 // (launch_dwpw_mfma, dwpw_mfma.hip).
 const char *launch_dwpw(const DwPwParams &p, hipStream_t s) {

@@ -44,6 +44,45 @@ __device__ __forceinline__ int64_t sample_offset(const ViewDesc &d, const FrameD
     return (int64_t)((uint64_t)iy * f.stride + (uint64_t)ix * 4);
 }
 
+// sample_offset split by what each operation depends on, for kernels that sample a whole patch:
+// everything up to the rotation's two products depends on x alone or on y alone, so a patch of
+// R rows and C columns needs R + C of those (two f32 divisions and a round each) instead of
+// R * C.  sample_col(x) gives {0 + cos * vx, 0 + sin * vx}, sample_row(y) gives {-sin * vy,
+// cos * vy}; sample_join adds them and finishes exactly as sample_offset does -- the same
+// operations on the same values in the same order, so the same bits.
+__device__ __forceinline__ float2 sample_col(const ViewDesc &d, int x, int ow) {
+#pragma clang fp contract(off)
+    const float u = (float)x / (float)ow;
+    const uint32_t sx = sat_u32(roundf(u * d.view_w));
+    const float px = (float)sx + 0.5f;
+    const float vx = px - d.half_w;
+    return make_float2(0.f + d.cos_r * vx, 0.f + d.sin_r * vx);
+}
+
+__device__ __forceinline__ float2 sample_row(const ViewDesc &d, int y, int oh) {
+#pragma clang fp contract(off)
+    const float w = (float)y / (float)oh;
+    const uint32_t sy = sat_u32(roundf(w * d.view_h));
+    const float py = (float)sy + 0.5f;
+    const float vy = py - d.half_h;
+    const float ns = -d.sin_r;
+    return make_float2(ns * vy, d.cos_r * vy);
+}
+
+__device__ __forceinline__ int64_t sample_join(const ViewDesc &d, const FrameDesc &f, float2 col, float2 row) {
+#pragma clang fp contract(off)
+    const float rx = col.x + row.x;
+    const float ry = col.y + row.y;
+    const float ox = (rx + d.half_w) + d.tl_x;
+    const float oy = (ry + d.half_h) + d.tl_y;
+    const float fx = roundf(ox - 0.5f), fy = roundf(oy - 0.5f);
+
+    if (fx < 0.f || fy < 0.f || ceilf(fx) >= 4294967296.f || ceilf(fy) >= 4294967296.f) return -1;
+    const uint32_t ix = (uint32_t)roundf(fx), iy = (uint32_t)roundf(fy);
+    if (ix >= f.w || iy >= f.h) return -1;
+    return (int64_t)((uint64_t)iy * f.stride + (uint64_t)ix * 4);
+}
+
 // The frame a view samples.  Device-built view tables (zr_cnn_estimate_device_views_async) are
 // not range-checked on the host: an index past the frame table samples a 0x0 frame (every
 // pixel Color::NONE) through frame 0's valid pointer instead of reading past the table.

@@ -85,6 +85,7 @@ class Compiler {
     void fuse_dw_gap();
     void group_siblings();
     void mark_inverted_residuals();
+    void mark_stem_blocks();
     void allocate();
 };
 
@@ -927,6 +928,25 @@ void Compiler::mark_inverted_residuals() {
     }
 }
 
+// Stem -> (depthwise -> 1x1) pairs where the block alone reads the stem's output, as its input and
+// as its residual: the executor may launch them as one kernel (stemblock.hip), the stem tensor
+// kept in LDS.  Its storage stays allocated: the unfused launches need it.
+void Compiler::mark_stem_blocks() {
+    std::vector<int> reads(P.storage_size.size(), 0);
+    for (const Step &s : P.steps)
+        for (const TRef *r : {&s.in, &s.in2})
+            if (r->kind == 0 && r->id >= 0) reads[r->id]++;
+    for (size_t i = 0; i + 1 < P.steps.size(); i++) {
+        Step &e = P.steps[i];
+        const Step &d = P.steps[i + 1];
+        // (reads: the block's input and its residual are the two reads of the stem's output)
+        e.sb = e.kind == S_DIRECT && e.stem && e.M <= 32 && e.group == 1 && d.group == 1 && e.out.kind == 0 &&
+               e.out.c_off == 0 && d.kind == S_DWPW && d.in.kind == 0 && d.in.id == e.out.id && d.in.c_off == 0 &&
+               d.res_mode != 0 && d.in2.kind == 0 && d.in2.id == e.out.id && d.in2.c_off == 0 &&
+               reads[e.out.id] == 2;
+    }
+}
+
 void Compiler::group_siblings() {
     const int n = (int)P.steps.size();
     if (n < 2) return;
@@ -1011,7 +1031,7 @@ void Compiler::allocate() {
     // a fused inverted residual (Step::ir) reads the expand's input and writes the projection's
     // output in ONE launch: the two must not share memory, so each is live across both steps
     for (size_t i = 0; i + 1 < P.steps.size(); i++) {
-        if (!P.steps[i].ir) continue;
+        if (!P.steps[i].ir && !P.steps[i].sb) continue;  // (a fused stem + block: the same)
         const TRef &x = P.steps[i].in, &o = P.steps[i + 1].out;
         if (x.kind == 0 && x.id >= 0) last[x.id] = std::max(last[x.id], tof[i + 1]);
         if (o.kind == 0 && o.id >= 0) first[o.id] = std::min(first[o.id], tof[i]);
@@ -1120,6 +1140,7 @@ bool Compiler::run(const std::vector<uint32_t> &sel) {
     if (form_on(FORM_DWGAP)) fuse_dw_gap();
     if (form_on(FORM_GROUPS)) group_siblings();
     if (form_on(FORM_IR)) mark_inverted_residuals();
+    if (form_on(FORM_STEMBLOCK)) mark_stem_blocks();
     allocate();
     return true;
 }
@@ -1267,8 +1288,49 @@ void run_plan(const Plan &plan, const Binding &b, hipStream_t stream, LaunchHook
         g.nact = b.nact;
         return d;
     };
+    auto stem_of = [&](const Step &s, bool pre) {
+        Resolved out = resolve(s.out, plan, b);
+        StemParams sp{};
+        if (pre) sp.pre = *b.pre;
+        else sp.in = plane_of(s.in, plan, b);
+        sp.out = const_cast<float *>(out.p);
+        sp.o_sN = out.sN;
+        sp.o_sC = out.sC;
+        sp.IH = s.in.H;
+        sp.IW = s.in.W;
+        sp.OH = s.out.H;
+        sp.OW = s.out.W;
+        sp.N = b.N;
+        sp.Cout = s.M;
+        sp.k = s.kh;
+        sp.stride = s.stride;
+        sp.pad_t = s.pad_t;
+        sp.pad_l = s.pad_l;
+        sp.w = W + s.w_off;
+        sp.bias = W + s.b_off;
+        sp.act = act_of(s.pre, W);
+        sp.nact = b.nact;
+        return sp;
+    };
     for (size_t si = 0; si < plan.steps.size(); ++si) {
         const Step &s = plan.steps[si];
+        if (s.sb && si + 1 < plan.steps.size()) {
+            // stem + first block in one launch (mark_stem_blocks); nullptr: the pair does not fit
+            // the fused kernel, so both run on their own below
+            const Step &s2 = plan.steps[si + 1];
+            const bool pre = s.in.kind == 1 && b.pre;
+            if (hook) hook->before(stream);
+            const char *kname = launch_stem_dwpw(stem_of(s, pre), pre, dwpw_of(s2), stream);
+            if (kname) {
+                // fused-boundary bytes: the stem's input and the block's output (the stem tensor's
+                // write and read gone); FLOPs of both steps, the recomputed halo not counted
+                const double bytes = (pre ? s.bytes_pre : s.bytes) + s2.bytes - 8.0 * (double)s.out.C * s.out.H * s.out.W;
+                if (hook) hook->after(stream, kname, bytes * b.N, (s.flops + s2.flops) * b.N);
+                ++si;
+                continue;
+            }
+            if (hook) hook->cancel();
+        }
         if (s.ir && si + 1 < plan.steps.size()) {
             // expand + depthwise + projection in one launch (mark_inverted_residuals); nullptr: the
             // shapes do not fit the fused kernel, so both run on their own below
@@ -1344,28 +1406,8 @@ void run_plan(const Plan &plan, const Binding &b, hipStream_t stream, LaunchHook
         }
         case S_DIRECT: {
             if (s.stem) {
-                StemParams sp{};
                 const bool pre = s.in.kind == 1 && b.pre;
-                if (pre) sp.pre = *b.pre;
-                else sp.in = plane_of(s.in, plan, b);
-                sp.out = const_cast<float *>(out.p);
-                sp.o_sN = out.sN;
-                sp.o_sC = out.sC;
-                sp.IH = s.in.H;
-                sp.IW = s.in.W;
-                sp.OH = s.out.H;
-                sp.OW = s.out.W;
-                sp.N = b.N;
-                sp.Cout = s.M;
-                sp.k = s.kh;
-                sp.stride = s.stride;
-                sp.pad_t = s.pad_t;
-                sp.pad_l = s.pad_l;
-                sp.w = W + s.w_off;
-                sp.bias = W + s.b_off;
-                sp.act = act_of(s.pre, W);
-                sp.nact = b.nact;
-                kname = launch_stem(sp, pre, stream);
+                kname = launch_stem(stem_of(s, pre), pre, stream);
                 if (hook) hook->after(stream, kname, (pre ? s.bytes_pre : s.bytes) * b.N, s.flops * b.N);
                 continue;
             }

@@ -67,6 +67,9 @@ struct Step {
     // mark_inverted_residuals: 1 = this expand (S_GEMM) and the next step (S_DWPW, its only reader)
     // may run as one launch (launch_ir), the expanded tensor never stored
     int ir = 0;
+    // mark_stem_blocks: 1 = this stem (S_DIRECT) and the next step (S_DWPW, its only reader, with
+    // the stem's output as input and residual) may run as one launch (launch_stem_dwpw)
+    int sb = 0;
 };
 
 struct PlanOutput {

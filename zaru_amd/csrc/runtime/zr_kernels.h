@@ -216,7 +216,8 @@ struct DwPwParams {
 //   ir: expand 1x1 + depthwise + projection in one launch (plan.cpp mark_inverted_residuals, ir.hip)
 //   bneck: FaceMesh V2's reduction 1x1 + depthwise + 1x1 + residual in one launch (bneck.hip)
 //   pin: the row-task depthwise's window reads at full width (ds_read_b64 / b128, dwpw_dma_pin_kernel)
-enum Form : int { FORM_DMA, FORM_V4, FORM_VALU, FORM_VALU_DB, FORM_ROWS, FORM_VRES, FORM_VSTORE, FORM_WS, FORM_GROUPS, FORM_DWGAP, FORM_RT, FORM_IR, FORM_IRL, FORM_IRL2, FORM_BNECK, FORM_PIN, FORM_COUNT };
+//   stemblock: the stem conv + the first BlazeBlock in one launch (plan.cpp mark_stem_blocks, stemblock.hip)
+enum Form : int { FORM_DMA, FORM_V4, FORM_VALU, FORM_VALU_DB, FORM_ROWS, FORM_VRES, FORM_VSTORE, FORM_WS, FORM_GROUPS, FORM_DWGAP, FORM_RT, FORM_IR, FORM_IRL, FORM_IRL2, FORM_BNECK, FORM_PIN, FORM_STEMBLOCK, FORM_COUNT };
 bool form_on(Form f);
 
 bool stem_supported(int cin, int k, int stride, int cout);
@@ -263,5 +264,12 @@ const char *launch_irl(const GemmParams &e, const DwPwParams &d, hipStream_t s);
 // FaceMesh V2's bottleneck pair (a C -> C/2 reduction feeding a 3x3 dwpw back to C with the
 // reduction's input as residual) in one launch (bneck.hip); nullptr when the shapes do not fit
 const char *launch_bneck(const GemmParams &e, const DwPwParams &d, hipStream_t s);
+
+// A stem (p / pre as for launch_stem) and the depthwise + 1x1 step that alone reads its output
+// (d) in one launch, the stem tile kept in LDS (stemblock.hip); nullptr when the pair does not fit
+// (the caller launches both)
+const char *launch_stem_dwpw(const StemParams &p, bool pre, const DwPwParams &d, hipStream_t s);
+// whether launch_dwpw runs p as dwpw_vres_kernel's stride-1 case (residual = the centre tap)
+bool dwpw_is_vres1(const DwPwParams &p);
 
 }  // namespace zr
