@@ -274,6 +274,64 @@ int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, cons
 int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
                                     const float *d_positions, const float *d_flag, size_t flag_stride,
                                     float *d_lm_out, zr_view_desc *d_views, void *hip_stream);
+
+/* ---- Head pose: Procrustes analysis of landmark sets (crates/zaru/src/procrustes.rs) ---------
+ * ProcrustesAnalyzer on the device: the similarity transform (scale, rotation, translation) that
+ * maps a reference point set onto each of n_sets landmark sets, e.g. the canonical face mesh onto
+ * a FaceMesh result (the reference's own acceptance test, face/landmark/mediapipe.rs:589-600), so
+ * a device loop gets head orientation without copying n x 468 x 3 floats to the host per frame.
+ * The caller supplies the reference points; no mesh ships with the library.
+ * The arithmetic is f32 in a fixed operation order (csrc/kernels/procrustes_math.h), one rounding
+ * per operation, bit-identical to the host mirror (host/procrustes.cpp):
+ *     centroid    three running sums from 0 over the points in index order, each / (float)N;
+ *                 p[k] -= centroid                                          (procrustes.rs:165-175)
+ *     scale       s += (x*x + y*y) + z*z in index order; s /= (float)N; s = sqrt(s);
+ *                 p[k] /= s, a division per component                               (:182-195)
+ *                 (centroid and scale are bit-exact with the reference's own loops)
+ *     covariance  M[r][c] = sum_k p[k][r] * q[k][c], k ascending, product and sum rounded
+ *                 separately; q = the reference after the same two steps.  The reference's GEMM
+ *                 order is unspecified; this order is this library's.
+ *     rotation    R = U diag(1, 1, d) V^T, d = sign(det(V^T U)), from an SVD of M (:138-161):
+ *                 a cyclic one-sided Jacobi with a fixed number of sweeps (no convergence loop: NaN
+ *                 or all-zero input takes the same path), columns ordered by norm, the third
+ *                 column of U and V the cross product of the first two.  Data scale == 0: R = I.
+ *     quaternion  the four-branch conversion on tr = R00 + R11 + R22 (nalgebra's
+ *                 from_rotation_matrix), stored {i, j, k, w}; the sign is not normalised.
+ *     result      scale = data scale / reference scale;
+ *                 translation = centroid - (R * ref_centroid) * scale, row dot products left to
+ *                 right (:116-136; the reference rotates by the quaternion, here by R).
+ * With flip_y a point is (x, -y, z), applied on load (the reference test's flip into the
+ * canonical mesh's Y-up coordinates).  Any NaN in a record is the quiet NaN 0x7fc00000. */
+typedef struct zr_procrustes zr_procrustes; /* the reference set: centroid, scale, normalised q in HBM */
+#define ZR_PROCRUSTES_MAX_POINTS 2048       /* the kernel stages a set and the reference in LDS */
+/* ref_xyz: n_ref x 3 host floats.  Refused with ZR_ERR_INVALID_ARGUMENT: NULL ref_xyz or out,
+ * n_ref < 2, n_ref > ZR_PROCRUSTES_MAX_POINTS, a non-finite reference point.  The reference is
+ * uploaded to the current device before the call returns. */
+int zr_procrustes_create(const float *ref_xyz, size_t n_ref, zr_procrustes **out);
+void zr_procrustes_destroy(zr_procrustes *p);
+typedef struct {
+    float centroid[3];    /* of the analysed points; rotation and scaling happen around it */
+    float scale;          /* relative to the reference */
+    float translation[3]; /* with the rotated, scaled reference centroid taken out */
+    uint32_t valid;       /* 0: the set was not analysed and every float is NaN */
+    float quat[4];        /* i, j, k, w */
+    float rot[9];         /* row-major; x -> centroid + scale * rot * (x - ref_centroid) */
+} zr_pose;
+/* Set i is the stride floats at d_points + i * stride and analyses its first n_ref points
+ * (FaceMesh V2's 478 landmarks against a 468-point mesh: stride 1434).  d_valid may be NULL;
+ * else int32 per set, and d_valid[i] == 0 writes valid = 0 and NaN into every float of record i
+ * without any arithmetic.  Otherwise valid = 1, whatever the points hold: a non-finite point
+ * gives NaN values, a set collapsed onto one point gives scale 0 and the identity rotation.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: NULL p, d_points or d_out, n_sets == 0,
+ * stride < 3 n_ref, n_sets or stride above 2^31 - 1 (the kernel's 32-bit set index and stride). */
+int zr_procrustes_analyze_async(const zr_procrustes *p, const float *d_points, size_t n_sets, size_t stride,
+                                int flip_y, const int32_t *d_valid, zr_pose *d_out, void *hip_stream);
+/* The same over a device loop's landmarks (zr_track_update_async's d_lm_out): set i is analysed
+ * when d_state[i].tracked != 0, so a stream not tracked this step gets valid = 0. */
+int zr_procrustes_analyze_tracked_async(const zr_procrustes *p, const float *d_points, size_t n_sets,
+                                        size_t stride, int flip_y, const zr_track_state *d_state,
+                                        zr_pose *d_out, void *hip_stream);
+
 /* The sampling parameters the preprocessing derives from each zr_view: glibc cosf/sinf of the
  * angle (rect.rs:135-137,417-423), so a caller can build or check a device view table.  A view
  * whose frame index is past the call's frame table samples Color::NONE everywhere. */

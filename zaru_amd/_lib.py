@@ -63,6 +63,13 @@ class LmFilter(C.Structure):
         return f
 
 
+class Pose(C.Structure):
+    """zr_pose: the Procrustes result of one point set (84 bytes).  `quat` is {i, j, k, w}, `rot`
+    row-major; valid == 0: the set was not analysed and every float is NaN."""
+    _fields_ = [("centroid", C.c_float * 3), ("scale", C.c_float), ("translation", C.c_float * 3),
+                ("valid", C.c_uint32), ("quat", C.c_float * 4), ("rot", C.c_float * 9)]
+
+
 def lm_filter_state_size(f: LmFilter, num_landmarks: int) -> int:
     n = C.c_size_t(0)
     check(lib().zr_lm_filter_state_size(C.byref(f), num_landmarks, C.byref(n)))
@@ -89,6 +96,10 @@ SIGNATURES = [
     ("zr_lm_filter_state_size", _I, [_P, _SZ, C.POINTER(_SZ)]),
     ("zr_lm_filter_async", _I, [_P, _P, _P, _SZ, _P, _SZ, _P, _SZ, _F, _P, _P, _P]),
     ("zr_track_update_positions_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P]),
+    ("zr_procrustes_create", _I, [_P, _SZ, C.POINTER(_P)]),
+    ("zr_procrustes_destroy", None, [_P]),
+    ("zr_procrustes_analyze_async", _I, [_P, _P, _SZ, _SZ, _I, _P, _P, _P]),
+    ("zr_procrustes_analyze_tracked_async", _I, [_P, _P, _SZ, _SZ, _I, _P, _P, _P]),
     ("zr_view_describe", _I, [_P, _SZ, _U32, _P]),
     ("zr_detect_post_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _U32, _U32, _P, _P]),
     ("zr_detect_post_mapped_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _P]),
@@ -217,6 +228,50 @@ class DeviceBuffer:
 
     def __del__(self):
         self.free()
+
+
+class Procrustes:
+    """zr_procrustes: a reference point set ((n, 3) float32, n >= 2) on the device, and the batched
+    analysis of device-resident point sets against it (kernels/procrustes.hip)."""
+
+    def __init__(self, reference):
+        import numpy as np
+        ref = np.ascontiguousarray(reference, np.float32)
+        if ref.ndim != 2 or ref.shape[1] != 3:
+            raise ZaruError(-4, "reference must be (n, 3) float32")
+        p = C.c_void_p()
+        check(lib().zr_procrustes_create(ref.ctypes.data, ref.shape[0], C.byref(p)))
+        self.ptr, self.n_ref = p.value, ref.shape[0]
+
+    def analyze_async(self, d_points: int, n_sets: int, d_out: int, stride=None, flip_y=False, d_valid=None,
+                      stream=None):
+        """Enqueue the analysis of n_sets sets (`stride` floats apart, default 3 n_ref) into n_sets
+        zr_pose records at d_out."""
+        check(lib().zr_procrustes_analyze_async(self.ptr, d_points, n_sets,
+                                                3 * self.n_ref if stride is None else stride,
+                                                int(bool(flip_y)), d_valid, d_out, stream))
+
+    def analyze(self, points, flip_y=False, valid=None):
+        """Host arrays in, a numpy record array (dtype of `Pose`) out: points is (n_sets, m, 3)
+        float32 with m >= n_ref; valid an optional int32 mask."""
+        import numpy as np
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 3 or pts.shape[2] != 3:
+            raise ZaruError(-4, "points must be (n_sets, m, 3) float32")
+        d_pts = DeviceBuffer.from_array(pts)
+        d_valid = None if valid is None else DeviceBuffer.from_array(np.ascontiguousarray(valid, np.int32))
+        d_out = DeviceBuffer(pts.shape[0] * C.sizeof(Pose))
+        self.analyze_async(d_pts.ptr, pts.shape[0], d_out.ptr, 3 * pts.shape[1], flip_y,
+                           None if d_valid is None else d_valid.ptr)
+        return d_out.download((pts.shape[0],), np.dtype(Pose))
+
+    def close(self):
+        if getattr(self, "ptr", None) and _LIB is not None:
+            _LIB.zr_procrustes_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        self.close()
 
 
 def synchronize(stream=None):

@@ -10,6 +10,7 @@
 #include "device_hand_tracker.h"
 #include "landmark.h"
 #include "pipeline.h"
+#include "procrustes.h"
 #include "recognition.h"
 #include "device_face_loop.h"
 #include "device_tracker.h"
@@ -64,6 +65,31 @@ LandmarkNetwork landmark_net(const std::string &name) {
     if (name == "face68_peppa") return LandmarkNetwork::peppa_68();
     throw ZaruError(ZR_ERR_INVALID_ARGUMENT,
                     "landmark network must be 'facemesh', 'facemesh_v2', 'hand', 'eye', 'face68_pfld' or 'face68_peppa'");
+}
+
+py::array_t<float> f32_array(const float *v, std::vector<py::ssize_t> shape) {
+    py::array_t<float> a(shape);
+    std::memcpy(a.mutable_data(), v, (size_t)a.size() * 4);
+    return a;
+}
+
+// set_pose_reference's argument: None / empty (off) or (n, 3) float32 points
+std::vector<float> pose_reference_arg(const py::object &o) {
+    if (o.is_none()) return {};
+    auto a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(o);
+    if (!a) throw ZaruError(ZR_ERR_SHAPE, "pose reference must be None or (n, 3) float32");
+    if (a.size() == 0) return {};
+    if (a.ndim() != 2 || a.shape(1) != 3) throw ZaruError(ZR_ERR_SHAPE, "pose reference must be None or (n, 3) float32");
+    return std::vector<float>(a.data(), a.data() + a.size());
+}
+
+// poses(): (n, 21) f32 view of the zr_pose records {centroid[3], scale, translation[3], valid
+// (uint32 bits), quat[4] = i j k w, rot[9] row-major}; zaru_amd._lib.Pose is the same layout
+py::array_t<float> poses_array(const std::vector<zr_pose> &v) {
+    static_assert(sizeof(zr_pose) == 84, "zr_pose");
+    py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)21});
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(zr_pose));
+    return a;
 }
 
 // set_filter's argument: None, Ema, AlphaBeta or OneEuro
@@ -292,6 +318,40 @@ PYBIND11_MODULE(_zaru_host, m) {
             return out;
         }, py::arg("positions"), py::arg("elapsed") = Estimator::DEFAULT_FILTER_DT);
 
+    // crates/zaru/src/procrustes.rs: the similarity transform from reference points to data points
+    // (head pose of a face mesh against the canonical mesh); kernels/procrustes_math.h on the host
+    py::class_<AnalysisResult>(m, "AnalysisResult")
+        .def_property_readonly("centroid", [](const AnalysisResult &r) { return f32_array(r.centroid.data(), {3}); })
+        .def_property_readonly("translation", [](const AnalysisResult &r) { return f32_array(r.translation.data(), {3}); })
+        .def_readonly("scale", &AnalysisResult::scale)
+        .def_property_readonly("rotation", [](const AnalysisResult &r) { return f32_array(r.rotation.data(), {4}); })
+        .def_property_readonly("rotation_matrix",
+                               [](const AnalysisResult &r) { return f32_array(r.rotation_matrix.data(), {3, 3}); })
+        .def("transform", [](const AnalysisResult &r) { return f32_array(r.transform().data(), {4, 4}); })
+        .def("euler_angles", [](const AnalysisResult &r) {
+            const auto e = r.euler_angles();
+            return py::make_tuple(e[0], e[1], e[2]);  // roll, pitch, yaw (radians)
+        })
+        // the record as the device writes it: 21 x f32 view of zr_pose (word 7 is `valid`)
+        .def("pose", [](const AnalysisResult &r) {
+            const zr_pose p = r.pose();
+            return f32_array(reinterpret_cast<const float *>(&p), {21});
+        });
+    py::class_<ProcrustesAnalyzer>(m, "ProcrustesAnalyzer")
+        .def(py::init([](py::array_t<float, py::array::c_style | py::array::forcecast> ref) {
+                 if (ref.ndim() != 2 || ref.shape(1) != 3) throw ZaruError(ZR_ERR_SHAPE, "reference must be (n, 3) float32");
+                 return new ProcrustesAnalyzer(ref.data(), (size_t)ref.shape(0));
+             }), py::arg("reference"))
+        .def("__len__", &ProcrustesAnalyzer::size)
+        .def_property_readonly("reference_centroid",
+                               [](const ProcrustesAnalyzer &a) { return f32_array(a.reference_centroid().data(), {3}); })
+        .def_property_readonly("reference_scale", &ProcrustesAnalyzer::reference_scale)
+        .def("analyze", [](ProcrustesAnalyzer &a, py::array_t<float, py::array::c_style | py::array::forcecast> pts,
+                           bool flip_y) {
+            if (pts.ndim() != 2 || pts.shape(1) != 3) throw ZaruError(ZR_ERR_SHAPE, "points must be (n, 3) float32");
+            return a.analyze(pts.data(), (size_t)pts.shape(0), flip_y);
+        }, py::arg("points"), py::arg("flip_y") = false);
+
     py::class_<Estimator>(m, "Estimator")
         .def(py::init([](const std::string &net, int device) { return new Estimator(landmark_net(net), device); }),
              py::arg("network") = "facemesh", py::arg("device") = 0)
@@ -430,6 +490,10 @@ PYBIND11_MODULE(_zaru_host, m) {
         }, py::arg("frames"), py::arg("elapsed") = py::none())
         .def("set_filter", [](DeviceTracker &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
              py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
+        .def("set_pose_reference", [](DeviceTracker &t, const py::object &points, bool flip_y) {
+            t.set_pose_reference(pose_reference_arg(points), flip_y);
+        }, py::arg("points"), py::arg("flip_y") = true)
+        .def("poses", [](DeviceTracker &t) { return poses_array(t.poses()); })
         .def("synchronize", &DeviceTracker::synchronize, py::call_guard<py::gil_scoped_release>())
         .def("__len__", &DeviceTracker::size)
         .def("states", [](DeviceTracker &t) {
@@ -485,6 +549,10 @@ PYBIND11_MODULE(_zaru_host, m) {
         }, py::arg("frames"), py::arg("elapsed") = py::none())
         .def("set_filter", [](DeviceFaceLoop &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
              py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
+        .def("set_pose_reference", [](DeviceFaceLoop &t, const py::object &points, bool flip_y) {
+            t.set_pose_reference(pose_reference_arg(points), flip_y);
+        }, py::arg("points"), py::arg("flip_y") = true)
+        .def("poses", [](DeviceFaceLoop &t) { return poses_array(t.poses()); })
         .def("synchronize", &DeviceFaceLoop::synchronize, py::call_guard<py::gil_scoped_release>())
         .def("__len__", &DeviceFaceLoop::streams)
         .def("states", [](DeviceFaceLoop &t) {

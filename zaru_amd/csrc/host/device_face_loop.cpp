@@ -109,6 +109,12 @@ void DeviceFaceLoop::set_filter(const std::optional<FilterParams> &f, float dt) 
     filter_.set(f, dt, (size_t)lm_net_.num_landmarks, n_, stream_);
 }
 
+void DeviceFaceLoop::set_pose_reference(const std::vector<float> &points, bool flip_y) {
+    pose_.set(points, flip_y, (size_t)lm_net_.num_landmarks, stream_);
+}
+
+std::vector<zr_pose> DeviceFaceLoop::poses() { return pose_.read(n_, stream_); }
+
 void DeviceFaceLoop::step(const std::vector<Image> &frames, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
     const float el = filter_.on() ? filter_.elapsed(elapsed) : 0.f;  // checked before anything is enqueued
@@ -166,6 +172,8 @@ void DeviceFaceLoop::step(const std::vector<Image> &frames, std::optional<float>
                                     lm_outs_[1].ptr, (size_t)ln.output_per_image(1), lm_out_.ptr, views_.ptr,
                                     stream_));
     }
+    // the head pose of the streams tracked this frame, over their frame-space landmarks
+    if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, n_, (size_t)lm_net_.num_landmarks, stream_);
     // 3-4: detector.detect on the streams whose track returned None (facemesh.rs:43-47)
     check(zr_track_lost_compact_async(state_.ptr, n_, &det_tmpl_, due_.ptr, ndue_.ptr, due_views_.ptr,
                                       due_total_.ptr, stream_));

@@ -17,6 +17,8 @@
 // A stream with no RoI at construction detects on its first frame, as the demo starts.
 // With a landmark filter set (set_filter), step 2 is zr_lm_filter_async followed by
 // zr_track_update_positions_async: the RoI follows the filtered landmarks.
+// With a pose reference set (set_pose_reference), zr_procrustes_analyze_tracked_async follows
+// step 2 on the same stream: the head pose of every stream tracked this frame.
 #pragma once
 #include <memory>
 #include <utility>
@@ -48,6 +50,10 @@ class DeviceFaceLoop {
     // resets its state.  set_roi, tracking loss and the re-seeding leave the state alone, as the
     // reference does; an inactive stream runs no estimate, so its state waits unchanged.
     void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
+    // head pose of every stream against `points` (n x 3 floats, e.g. the canonical face mesh; empty:
+    // off, the default), over this frame's landmarks (the filtered ones when a filter is set);
+    // flip_y: a landmark is (x, -y, z).  Throws when the network has fewer landmarks.
+    void set_pose_reference(const std::vector<float> &points, bool flip_y = true);
     void synchronize();
     size_t streams() const { return n_; }
     const LandmarkNetwork &landmarker() const { return lm_net_; }
@@ -55,6 +61,7 @@ class DeviceFaceLoop {
     // after synchronize():
     std::vector<zr_track_state> states();       // tracked = this frame's track() returned Some
     std::vector<float> landmarks();             // this frame, frame px, n x L x 3 (NaN: not tracked)
+    std::vector<zr_pose> poses();               // this frame's head poses (valid 0: not tracked)
     std::vector<int32_t> detected();            // per stream: 1 if this frame ran the detector
     std::vector<int32_t> detection_counts();    // per stream: faces this frame's detection found
     uint64_t detections_run();                  // detector images summed over the steps
@@ -79,6 +86,7 @@ class DeviceFaceLoop {
     DeviceArray<int32_t> due_, ndue_, count_;
     DeviceArray<uint64_t> due_total_, reseeded_;
     DeviceFilter filter_;
+    DevicePose pose_;
 };
 
 }  // namespace zh

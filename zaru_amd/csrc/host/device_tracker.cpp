@@ -46,6 +46,47 @@ float DeviceFilter::elapsed(const std::optional<float> &e) const {
     return el;
 }
 
+DevicePose::~DevicePose() {
+    if (ref) zr_procrustes_destroy(ref);
+}
+
+void DevicePose::set(const std::vector<float> &points, bool flip, size_t num_landmarks, void *stream) {
+    if (points.size() % 3) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "pose reference must be n x 3 floats");
+    const size_t n = points.size() / 3;
+    if (n > num_landmarks)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the network has fewer landmarks than the pose reference");
+    zr_procrustes *fresh = nullptr;
+    if (n) check(zr_procrustes_create(points.data(), n, &fresh));
+    if (ref) {
+        (void)zr_stream_synchronize(stream);  // an enqueued step may still read the old reference
+        zr_procrustes_destroy(ref);
+    }
+    ref = fresh;
+    n_ref = n;
+    flip_y = flip;
+    ran = false;
+}
+
+void DevicePose::enqueue(const zr_track_state *d_state, const float *d_landmarks, size_t n, size_t num_landmarks,
+                         void *stream) {
+    if (n > out.n) {  // a grown array is a new allocation: nothing enqueued may still use the old one
+        check(zr_stream_synchronize(stream));
+        out.resize(n);
+    }
+    check(zr_procrustes_analyze_tracked_async(ref, d_landmarks, n, 3 * num_landmarks, flip_y ? 1 : 0, d_state, out.ptr,
+                                              stream));
+    ran = true;
+}
+
+std::vector<zr_pose> DevicePose::read(size_t n, void *stream) {
+    if (!on()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "no pose reference set (set_pose_reference)");
+    if (!ran || n > out.n) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "no step has run since the pose reference was set");
+    std::vector<zr_pose> h(n);
+    if (n) check(zr_memcpy_async(h.data(), out.ptr, n * sizeof(zr_pose), 1, stream));
+    check(zr_stream_synchronize(stream));
+    return h;
+}
+
 DeviceTracker::DeviceTracker(LandmarkNetwork net, int device, float padding, float loss_thresh)
     : net_(net), cnn_(network_cnn(net.kind, device)) {
     if (!(padding >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "roi padding must be >= 0");
@@ -126,12 +167,20 @@ void DeviceTracker::step(const std::vector<Image> &frames, std::optional<float> 
                                               flagged ? outs_[1].ptr : nullptr,
                                               flagged ? (size_t)nn.output_per_image(1) : 0, lm_out_.ptr, views_.ptr,
                                               stream_));
-        return;
+    } else {
+        check(zr_track_update_async(state_.ptr, n_, &cfg_, outs_[0].ptr, (size_t)nn.output_per_image(0),
+                                    flagged ? outs_[1].ptr : nullptr, flagged ? (size_t)nn.output_per_image(1) : 0,
+                                    lm_out_.ptr, views_.ptr, stream_));
     }
-    check(zr_track_update_async(state_.ptr, n_, &cfg_, outs_[0].ptr, (size_t)nn.output_per_image(0),
-                                flagged ? outs_[1].ptr : nullptr, flagged ? (size_t)nn.output_per_image(1) : 0,
-                                lm_out_.ptr, views_.ptr, stream_));
+    // the head pose of the streams tracked this step, over their frame-space landmarks
+    if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, n_, (size_t)net_.num_landmarks, stream_);
 }
+
+void DeviceTracker::set_pose_reference(const std::vector<float> &points, bool flip_y) {
+    pose_.set(points, flip_y, (size_t)net_.num_landmarks, stream_);
+}
+
+std::vector<zr_pose> DeviceTracker::poses() { return pose_.read(n_, stream_); }
 
 void DeviceTracker::synchronize() {
     if (stream_) check(zr_stream_synchronize(stream_));

@@ -35,6 +35,32 @@ struct DeviceFilter {
     float elapsed(const std::optional<float> &e) const;
 };
 
+// A device loop's head pose output (ProcrustesAnalyzer, crates/zaru/src/procrustes.rs, as the
+// reference's FaceMesh test uses it: face/landmark/mediapipe.rs:589-600): the reference set in HBM
+// and one zr_pose per stream.  With a reference set a step enqueues zr_procrustes_analyze_tracked_async
+// on the loop's stream after the tracker update, over the loop's frame-space landmarks (the
+// filtered ones when a filter is set); a stream not tracked that step gets valid = 0.  Without
+// one (the default) a step enqueues and allocates nothing for it.
+struct DevicePose {
+    zr_procrustes *ref = nullptr;
+    size_t n_ref = 0;
+    bool flip_y = true;
+    bool ran = false;  // a step has written `out` since the reference was set
+    DeviceArray<zr_pose> out;
+    DevicePose() = default;
+    DevicePose(const DevicePose &) = delete;
+    DevicePose &operator=(const DevicePose &) = delete;
+    ~DevicePose();
+    bool on() const { return ref != nullptr; }
+    // replace the reference (n x 3 floats; empty: off); throws when the network has fewer landmarks
+    void set(const std::vector<float> &points, bool flip_y, size_t num_landmarks, void *stream);
+    // the pose of `n` streams' landmarks (n x num_landmarks x 3) on `stream`
+    void enqueue(const zr_track_state *d_state, const float *d_landmarks, size_t n, size_t num_landmarks,
+                 void *stream);
+    // the last step's records (synchronises `stream`)
+    std::vector<zr_pose> read(size_t n, void *stream);
+};
+
 class DeviceTracker {
   public:
     DeviceTracker(LandmarkNetwork net, int device = 0, float padding = LandmarkTracker::DEFAULT_ROI_PADDING,
@@ -52,6 +78,11 @@ class DeviceTracker {
     // Estimator::set_filter for every stream (nullopt: none): replaces the filter and resets its
     // state.  set_rois leaves the filter state alone while the stream count stays the same.
     void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
+    // head pose of every stream against `points` (n x 3 floats, e.g. the canonical face mesh; empty:
+    // off, the default), analysing each stream's first n landmarks; flip_y: a landmark is (x, -y, z).
+    // Throws when the network has fewer landmarks than the reference.
+    void set_pose_reference(const std::vector<float> &points, bool flip_y = true);
+    std::vector<zr_pose> poses();              // last step, one per stream (valid 0: not tracked)
     void synchronize();
     size_t size() const { return n_; }
     const LandmarkNetwork &network() const { return net_; }
@@ -72,6 +103,7 @@ class DeviceTracker {
     DeviceArray<zr_view_desc> views_;
     DeviceArray<float> outs_[4], lm_out_;
     DeviceFilter filter_;
+    DevicePose pose_;
 };
 
 }  // namespace zh

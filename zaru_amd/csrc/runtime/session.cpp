@@ -18,6 +18,7 @@
 #include "onnx_model.h"
 #include "plan.h"
 #include "zr_track.h"
+#include "../kernels/procrustes_math.h"
 
 namespace {
 
@@ -780,6 +781,87 @@ int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, cons
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
+}
+
+// ---- Procrustes analysis of landmark sets (kernels/procrustes.hip)
+}  // extern "C"
+struct zr_procrustes {
+    float *d_q = nullptr;  // the normalised reference, n_ref x 3
+    size_t n_ref = 0;
+    float centroid[3] = {0.f, 0.f, 0.f};
+    float scale = 0.f;
+};
+static_assert(sizeof(zr_pose) == sizeof(zr::procrustes::Pose) && sizeof(zr_pose) == 84, "zr_pose layout");
+extern "C" {
+
+int zr_procrustes_create(const float *ref_xyz, size_t n_ref, zr_procrustes **out) {
+    return guarded([&]() -> int {
+        if (!ref_xyz || !out) return set_err(ZR_ERR_INVALID_ARGUMENT, "null reference points or out pointer");
+        if (n_ref < 2) return set_err(ZR_ERR_INVALID_ARGUMENT, "need at least 2 points for procrustes analysis");
+        if (n_ref > (size_t)ZR_PROCRUSTES_MAX_POINTS)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "more reference points than ZR_PROCRUSTES_MAX_POINTS");
+        for (size_t i = 0; i < 3 * n_ref; i++)
+            if (!std::isfinite(ref_xyz[i])) return set_err(ZR_ERR_INVALID_ARGUMENT, "non-finite reference point");
+        auto p = std::make_unique<zr_procrustes>();
+        std::vector<float> q(ref_xyz, ref_xyz + 3 * n_ref);
+        zr::procrustes::normalise(q.data(), (int)n_ref, p->centroid, &p->scale);
+        p->n_ref = n_ref;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_q), q.size() * sizeof(float)));
+        const hipError_t e = hipMemcpy(p->d_q, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p->d_q);
+            return set_err(ZR_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+        }
+        *out = p.release();
+        return ZR_OK;
+    });
+}
+
+void zr_procrustes_destroy(zr_procrustes *p) {
+    if (!p) return;
+    if (p->d_q) (void)hipFree(p->d_q);
+    delete p;
+}
+
+static int procrustes_analyze(const zr_procrustes *p, const float *d_points, size_t n_sets, size_t stride,
+                              int flip_y, const int32_t *d_valid, const zr_track_state *d_state, zr_pose *d_out,
+                              void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!p || !d_points || !d_out) return set_err(ZR_ERR_INVALID_ARGUMENT, "null analyzer, points or output");
+        if (n_sets == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "no point sets");
+        if (stride < 3 * p->n_ref) return set_err(ZR_ERR_INVALID_ARGUMENT, "stride below 3 floats per reference point");
+        if (n_sets > (size_t)INT32_MAX || stride > (size_t)INT32_MAX)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "set count or stride beyond the kernel's 32-bit indices; split it");
+        zr::ProcrustesParams k{};
+        k.points = d_points;
+        k.q = p->d_q;
+        k.valid = d_valid;
+        k.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        k.out = reinterpret_cast<zr::procrustes::Pose *>(d_out);
+        k.n_sets = (int)n_sets;
+        k.n_ref = (int)p->n_ref;
+        k.stride = (int)stride;
+        k.flip_y = flip_y != 0;
+        k.ref_cx = p->centroid[0];
+        k.ref_cy = p->centroid[1];
+        k.ref_cz = p->centroid[2];
+        k.ref_scale = p->scale;
+        zr::launch_procrustes(k, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_procrustes_analyze_async(const zr_procrustes *p, const float *d_points, size_t n_sets, size_t stride,
+                                int flip_y, const int32_t *d_valid, zr_pose *d_out, void *hip_stream) {
+    return procrustes_analyze(p, d_points, n_sets, stride, flip_y, d_valid, nullptr, d_out, hip_stream);
+}
+
+int zr_procrustes_analyze_tracked_async(const zr_procrustes *p, const float *d_points, size_t n_sets,
+                                        size_t stride, int flip_y, const zr_track_state *d_state,
+                                        zr_pose *d_out, void *hip_stream) {
+    if (!d_state) return guarded([&]() -> int { return set_err(ZR_ERR_INVALID_ARGUMENT, "null tracker states"); });
+    return procrustes_analyze(p, d_points, n_sets, stride, flip_y, nullptr, d_state, d_out, hip_stream);
 }
 
 static int detect_post_impl(const float *d_logits, const float *d_boxes, const float *d_anchors,

@@ -64,6 +64,25 @@ inline size_t lm_filter_words(int filter, size_t L) {
 }
 const char *launch_lm_filter(const LmFilterParams &p, hipStream_t s);
 
+// Procrustes analysis of landmark sets (kernels/procrustes.hip; crates/zaru/src/procrustes.rs):
+// one wavefront per set, the arithmetic of kernels/procrustes_math.h.
+namespace procrustes {
+struct Pose;
+}
+struct ProcrustesParams {
+    const float *points;       // n_sets x stride floats; a set analyses its first n_ref points
+    const float *q;            // the normalised reference, n_ref x 3
+    const int32_t *valid;      // null, or per set: 0 = not analysed (valid 0, NaN floats)
+    const TrackState *state;   // (valid == null) null, or per set: tracked == 0 = not analysed
+    procrustes::Pose *out;     // n_sets records
+    int n_sets, n_ref, stride;
+    int flip_y;                // a point is (x, -y, z)
+    float ref_cx, ref_cy, ref_cz, ref_scale;
+};
+enum { PROCRUSTES_MAX_POINTS = 2048 };  // (7 n + 16) floats of LDS per workgroup: 57,408 B at the limit
+size_t procrustes_lds(int n_ref);
+const char *launch_procrustes(const ProcrustesParams &p, hipStream_t s);
+
 // Detector::detect_impl after inference (detpost.hip): extract, weighted NMS, map to frame px.
 struct DetPostParams {
     const float *logits;    // [N][A] raw classificator logits
