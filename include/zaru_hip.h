@@ -228,6 +228,16 @@ int zr_track_seed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *c
 int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
                           const float *d_landmarks, size_t lm_stride, const float *d_flag,
                           size_t flag_stride, float *d_lm_out, zr_view_desc *d_views, void *hip_stream);
+/* zr_track_update_async when the estimates are not stored in ROI order: ROI i reads landmark
+ * output 0 and output 1 at image d_index[i] instead of image i (zr_slot_compact_async's d_dense_of,
+ * when the network ran on the packed live slots only).  d_index is read for active ROIs only, so
+ * an inactive ROI may hold anything there (-1); an active ROI whose index is outside [0, n) has no
+ * estimate and is lost this step (confidence NaN).  d_index == NULL is the identity: the call is
+ * then zr_track_update_async.  Same checks, same arithmetic, same outputs otherwise. */
+int zr_track_update_indexed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                  const float *d_landmarks, size_t lm_stride, const float *d_flag,
+                                  size_t flag_stride, const int32_t *d_index, float *d_lm_out,
+                                  zr_view_desc *d_views, void *hip_stream);
 
 /* ---- Landmark temporal filters (crates/zaru/src/filter, landmark.rs:142-202) on the device ----
  * Estimator::set_filter smooths the network's landmarks over time, per landmark and coordinate,
@@ -375,6 +385,41 @@ int zr_hand_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_hroi
                          const int32_t *d_count, const float *d_dets, size_t dcap,
                          const uint32_t *d_frame_size, size_t n, const zr_hand_cfg *cfg, double now_ms,
                          int init_clock, zr_view_desc *d_views, int32_t *d_dropped, void *hip_stream);
+/* The same bookkeeping for any detector / landmark network pair (the reference's TODO:
+ * "generalize HandTracker to allow tracking any type of object with a detector and landmarker
+ * network"): K objects per stream with stable u64 ids.  zr_hand_manage_async with one more knob:
+ * a started object's ROI is RotatedRect(det.rect.grow_rel(det_grow), use_angle ? det.angle : 0) --
+ * hands {1.5, 1} (tracking.rs:136,159), faces {0, 0} (examples/facemesh.rs:49-54: the detection's
+ * bounding rect, unrotated).  grow_rel runs for det_grow == 0 too, in the filter and the start
+ * alike.  One kernel serves both calls; arguments, checks and outputs as above (d_roi = d_hroi,
+ * d_nobjects = d_nhands). */
+typedef struct {
+    int slots;              /* K: object slots per stream, 1..64 */
+    float iou_thresh;       /* filter and de-duplication threshold (0.3) */
+    float det_grow;         /* grow_rel factor of a detection's rect, >= 0 */
+    int use_angle;          /* 0: a started object's ROI is unrotated */
+    double interval_ms;     /* redetection interval (300 ms) */
+    int aspect_w, aspect_h; /* the landmark network's aspect ratio */
+} zr_multi_cfg;
+int zr_multi_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_roi, int32_t *d_src,
+                          int32_t *d_nobjects, uint64_t *d_next_id, double *d_next_det, int32_t *d_det_pending,
+                          const int32_t *d_count, const float *d_dets, size_t dcap,
+                          const uint32_t *d_frame_size, size_t n, const zr_multi_cfg *cfg, double now_ms,
+                          int init_clock, zr_view_desc *d_views, int32_t *d_dropped, void *hip_stream);
+/* After the bookkeeping a stream's live objects occupy slots [s * slots, s * slots + d_counts[s])
+ * (d_counts = d_nobjects / d_nhands; values are clamped to 0..slots).  This packs them in
+ * stream-then-slot order so the landmark network runs on the live objects only: for the k-th live
+ * slot d_dense_views[k] = d_views[slot] and d_dense_of[slot] = k; idle slots get d_dense_of = -1;
+ * *d_nactive = the live slots, and *d_total += *d_nactive (d_total may be NULL).  Entries of
+ * d_dense_views at and past *d_nactive are not written.  d_dense_views / d_dense_of hold
+ * n_streams * slots entries.  One workgroup scans the counts in 1024-stream chunks, so the order
+ * is fixed; the count stays on the device (zr_cnn_estimate_device_views_count_async reads it, and
+ * zr_track_update_indexed_async finds each slot's estimate through d_dense_of).
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL pointer other than d_total,
+ * n_streams == 0, slots outside 1..64, n_streams * slots above 2^31 - 1. */
+int zr_slot_compact_async(const int32_t *d_counts, size_t n_streams, size_t slots, const zr_view_desc *d_views,
+                          zr_view_desc *d_dense_views, int32_t *d_dense_of, int32_t *d_nactive,
+                          uint64_t *d_total, void *hip_stream);
 /* Cnn::estimate (nn/mod.rs:118-126) with a device-resident view table (frames: host array). */
 int zr_cnn_estimate_device_views_async(zr_session *s, const zr_frame *frames, size_t n_frames,
                                        const zr_view_desc *d_views, size_t n_views, float lo,

@@ -49,6 +49,12 @@ class TrackCfg(C.Structure):
                 ("padding", C.c_float), ("rois_per_frame", C.c_int)]
 
 
+class MultiCfg(C.Structure):
+    """zr_multi_cfg: the K-objects-per-stream bookkeeping (zr_multi_manage_async)."""
+    _fields_ = [("slots", C.c_int), ("iou_thresh", C.c_float), ("det_grow", C.c_float), ("use_angle", C.c_int),
+                ("interval_ms", C.c_double), ("aspect_w", C.c_int), ("aspect_h", C.c_int)]
+
+
 class LmFilter(C.Structure):
     """zr_lm_filter: kind 0 none, 1 EMA {alpha}, 2 alpha-beta {alpha, beta}, 3 1 euro
     {min_cutoff, beta, d_cutoff}."""
@@ -110,6 +116,10 @@ SIGNATURES = [
     ("zr_track_seed_detections_async", _I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _F, _I, _P, _P, _P, _P]),
     ("zr_hand_manage_async", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, C.c_double, _I,
                                   _P, _P, _P]),
+    ("zr_multi_manage_async", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, C.c_double, _I,
+                                   _P, _P, _P]),
+    ("zr_slot_compact_async", _I, [_P, _SZ, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("zr_track_update_indexed_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_embed_match_async", _I, [_P, _SZ, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),

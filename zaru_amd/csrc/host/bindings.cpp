@@ -8,6 +8,7 @@
 #include "detection.h"
 #include "hand_tracker.h"
 #include "device_hand_tracker.h"
+#include "device_multi_tracker.h"
 #include "landmark.h"
 #include "pipeline.h"
 #include "procrustes.h"
@@ -464,6 +465,61 @@ PYBIND11_MODULE(_zaru_host, m) {
                 std::memcpy(a.mutable_data(), h.landmarks.data(), h.landmarks.size() * 4);
                 d["landmarks"] = a;
                 d["view_rect"] = h.view_rect;
+                out.append(d);
+            }
+            return out;
+        });
+    // K objects per stream with ids, for any detector / landmark network pair
+    py::class_<DeviceMultiTracker>(m, "DeviceMultiTracker")
+        .def(py::init([](const std::string &detector, const std::string &landmarker, size_t streams, int slots,
+                         int device) {
+                 return new DeviceMultiTracker(detector_net(detector), landmark_net(landmarker), streams, slots, device);
+             }), py::arg("detector") = "face", py::arg("landmarker") = "facemesh", py::arg("streams") = 1,
+             py::arg("slots") = 4, py::arg("device") = 0)
+        .def("set_redetect_interval", &DeviceMultiTracker::set_redetect_interval, py::arg("ms"))
+        .def("set_iou_thresh", &DeviceMultiTracker::set_iou_thresh)
+        .def("set_loss_threshold", &DeviceMultiTracker::set_loss_threshold)
+        .def("set_det_grow", &DeviceMultiTracker::set_det_grow)
+        .def("set_use_angle", &DeviceMultiTracker::set_use_angle, py::arg("on"))
+        .def("set_roi_padding", &DeviceMultiTracker::set_roi_padding)
+        .def("set_compact", &DeviceMultiTracker::set_compact, py::arg("on"))
+        .def("set_pose_reference", [](DeviceMultiTracker &t, const py::object &points, bool flip_y) {
+            t.set_pose_reference(pose_reference_arg(points), flip_y);
+        }, py::arg("points"), py::arg("flip_y") = true)
+        .def("inject_detections", &DeviceMultiTracker::inject_detections)
+        .def("step", [](DeviceMultiTracker &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
+                        double now_ms) {
+            const std::vector<Image> im = device_frames(frames);
+            py::gil_scoped_release nogil;
+            t.step(im, now_ms);
+        }, py::arg("frames"), py::arg("now_ms"))
+        // frames given as host arrays are refused by step (test hook for that rejection)
+        .def("step_host", [](DeviceMultiTracker &t, const std::vector<py::array_t<uint8_t, py::array::c_style>> &frames,
+                             double now_ms) {
+            std::vector<Image> im;
+            for (auto &f : frames) im.push_back(host_image(f));
+            t.step(im, now_ms);
+        }, py::arg("frames"), py::arg("now_ms"))
+        .def("synchronize", &DeviceMultiTracker::synchronize, py::call_guard<py::gil_scoped_release>())
+        .def("__len__", &DeviceMultiTracker::streams)
+        .def("slots", &DeviceMultiTracker::slots)
+        .def("object_counts", &DeviceMultiTracker::object_counts)
+        .def("detection_pending", &DeviceMultiTracker::detection_pending)
+        .def("dropped_objects", &DeviceMultiTracker::dropped_objects)
+        .def("dropped_detections", &DeviceMultiTracker::dropped_detections)
+        .def("detection_capacity", &DeviceMultiTracker::detection_capacity)
+        .def("detector_frames", &DeviceMultiTracker::detector_frames)
+        .def("landmark_images", &DeviceMultiTracker::landmark_images)
+        .def("objects", [](DeviceMultiTracker &t, size_t s) {
+            py::list out;
+            for (auto &o : t.objects(s)) {
+                py::dict d;
+                d["id"] = o.id;
+                d["landmarks"] = f32_array(o.landmarks.data(), {(py::ssize_t)(o.landmarks.size() / 3), (py::ssize_t)3});
+                d["view_rect"] = o.view_rect;
+                d["confidence"] = o.confidence;
+                // the zr_pose record as 21 x f32 (poses_array's layout), when a reference is set
+                if (o.pose) d["pose"] = f32_array(reinterpret_cast<const float *>(&*o.pose), {21});
                 out.append(d);
             }
             return out;

@@ -1,0 +1,327 @@
+// device_multi_tracker.cpp -- see device_multi_tracker.h.
+#include "device_multi_tracker.h"
+
+#include <algorithm>
+
+#include "hand_tracker.h"
+
+namespace zh {
+
+namespace {
+// checked before any network is loaded
+NetworkKind checked_landmarker(const LandmarkNetwork &lm, size_t streams, int slots) {
+    if (streams == 0 || slots <= 0 || slots > 64) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "bad stream / slot count");
+    const int kind = track_kind(lm.kind);
+    if (kind != 0 && kind != 1)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT,
+                        "the landmark network's estimate has no confidence: tracking cannot tell when an object is lost");
+    return lm.kind;
+}
+}  // namespace
+
+DeviceMultiTracker::DeviceMultiTracker(DetectorNetwork detector, LandmarkNetwork landmarker, size_t streams, int slots,
+                                       int device)
+    : det_(network_cnn(detector.kind, device)),
+      lm_(network_cnn(checked_landmarker(landmarker, streams, slots), device)), det_net_(detector),
+      lm_net_(landmarker) {
+    n_ = streams;
+    const bool face = is_face_detector(detector.kind);
+    const AspectRatio a = lm_->aspect();
+    cfg_.slots = slots;
+    cfg_.iou_thresh = HandTracker::DEFAULT_IOU_THRESH;
+    cfg_.det_grow = face ? 0.f : HandTracker::PALM_GROW;
+    cfg_.use_angle = face ? 0 : 1;
+    cfg_.interval_ms = HandTracker::DEFAULT_REDETECT_INTERVAL_MS;
+    cfg_.aspect_w = (int)a.w;
+    cfg_.aspect_h = (int)a.h;
+    tcfg_.kind = track_kind(landmarker.kind);
+    tcfg_.num_landmarks = landmarker.num_landmarks;
+    tcfg_.in_w = (int)lm_->input_width();
+    tcfg_.in_h = (int)lm_->input_height();
+    tcfg_.aspect_w = (int)a.w;
+    tcfg_.aspect_h = (int)a.h;
+    tcfg_.loss_thresh = LandmarkTracker::DEFAULT_LOSS_THRESHOLD;
+    tcfg_.padding = face ? LandmarkTracker::DEFAULT_ROI_PADDING : HandTracker::ROI_PADDING;
+    tcfg_.rois_per_frame = slots;
+    pcfg_.face = face ? 1 : 0;
+    pcfg_.anchors = (int)det_net_.anchors().size();
+    pcfg_.params = det_net_.params;
+    pcfg_.keypoints = det_net_.keypoints;
+    pcfg_.in_w = (int)det_->input_width();
+    pcfg_.in_h = (int)det_->input_height();
+    pcfg_.thresh = Detector::DEFAULT_THRESHOLD;
+    pcfg_.iou = NonMaxSuppression::DEFAULT_IOU_THRESH;
+    dcap_ = det_net_.anchors().size();
+    check(zr_stream_create(&stream_));
+    const size_t nv = n_ * (size_t)slots;
+    state_.resize(nv);
+    ids_.resize(nv);
+    roi_.resize(nv * 5);
+    src_.resize(nv);
+    views_.resize(nv);
+    dense_views_.resize(nv);
+    dense_of_.resize(nv);
+    nactive_.resize(1);
+    lm_total_.resize(1);
+    lm_out_.resize(nv * (size_t)lm_net_.num_landmarks * 3);
+    nobj_.resize(n_);
+    due_.resize(n_);
+    due_views_.resize(n_);
+    ndue_.resize(1);
+    due_total_.resize(1);
+    next_id_.resize(n_);
+    next_det_.resize(n_);
+    det_pending_.resize(n_);
+    count_.resize(n_);
+    dropped_.resize(n_);
+    fsize_.resize(2 * n_);
+    lbox_.resize(4 * n_);
+    dets_.resize(n_ * dcap_ * 20);
+    const NeuralNetwork &ln = lm_->nn();
+    for (size_t k = 0; k < ln.num_outputs() && k < 4; k++) outs_[k].resize((size_t)ln.output_per_image(k) * nv);
+    det_boxes_.resize(n_ * (size_t)pcfg_.anchors * pcfg_.params);
+    det_logits_.resize(n_ * (size_t)pcfg_.anchors);
+    const auto &an = det_net_.anchors();
+    anchors_.resize(2 * an.size());
+    check(zr_memcpy_async(anchors_.ptr, an.data(), an.size() * sizeof(Vec2), 0, stream_));
+    // no objects, no pending detection, ids from 0 (the state's `active` flags all clear)
+    const std::vector<zr_track_state> zs(nv, zr_track_state{});
+    check(zr_memcpy_async(state_.ptr, zs.data(), nv * sizeof(zr_track_state), 0, stream_));
+    const std::vector<int32_t> zi(n_, 0);
+    const std::vector<uint64_t> zl(n_, 0);
+    check(zr_memcpy_async(nobj_.ptr, zi.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(next_id_.ptr, zl.data(), n_ * 8, 0, stream_));
+    check(zr_memcpy_async(det_pending_.ptr, zi.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(count_.ptr, zi.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(dropped_.ptr, zi.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(nactive_.ptr, zi.data(), 4, 0, stream_));
+    check(zr_memcpy_async(due_total_.ptr, zl.data(), 8, 0, stream_));
+    check(zr_memcpy_async(lm_total_.ptr, zl.data(), 8, 0, stream_));
+    check(zr_stream_synchronize(stream_));  // the host vectors are pageable and go out of scope
+    injected_.resize(n_);
+}
+
+DeviceMultiTracker::~DeviceMultiTracker() {
+    if (stream_) {
+        (void)zr_stream_synchronize(stream_);
+        (void)zr_stream_destroy(stream_);
+    }
+}
+
+void DeviceMultiTracker::set_redetect_interval(double ms) {
+    if (!(ms >= 0.0)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "redetection interval must be >= 0");
+    cfg_.interval_ms = ms;
+}
+
+void DeviceMultiTracker::set_det_grow(float g) {
+    if (!(g >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "detection grow factor must be >= 0");
+    cfg_.det_grow = g;
+}
+
+void DeviceMultiTracker::set_roi_padding(float p) {
+    if (!(p >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "roi padding must be >= 0");
+    tcfg_.padding = p;
+}
+
+void DeviceMultiTracker::set_pose_reference(const std::vector<float> &points, bool flip_y) {
+    pose_.set(points, flip_y, (size_t)lm_net_.num_landmarks, stream_);
+}
+
+void DeviceMultiTracker::inject_detections(size_t s, const std::vector<Detection> &dets) {
+    if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
+    for (const Detection &d : dets) injected_[s].push_back(d);
+}
+
+// The detector's letterbox table and the frame sizes of this frame size, and a valid view in
+// every entry of the two packed view tables: the compaction kernels write only the first *count
+// entries, and a preprocessing that does not honour the device count (an unfused plan) samples
+// them all.
+void DeviceMultiTracker::frame_size(uint32_t W, uint32_t H) {
+    fw_ = W;
+    fh_ = H;
+    Rect lb;
+    const zr_view dv = to_zr_view(letterbox_view(W, H, det_->aspect(), &lb));
+    check(zr_view_describe(&dv, 1, 0, &det_tmpl_));
+    std::vector<float> l(4 * n_);
+    std::vector<uint32_t> fs(2 * n_);
+    for (size_t i = 0; i < n_; i++) {
+        l[4 * i] = lb.center().x;
+        l[4 * i + 1] = lb.center().y;
+        l[4 * i + 2] = lb.width();
+        l[4 * i + 3] = lb.height();
+        fs[2 * i] = W;
+        fs[2 * i + 1] = H;
+    }
+    const size_t K = (size_t)cfg_.slots, nv = n_ * K;
+    std::vector<zr_view_desc> due(n_, det_tmpl_), dense(nv, det_tmpl_);
+    for (size_t i = 0; i < n_; i++) due[i].frame = (uint32_t)i;
+    for (size_t i = 0; i < nv; i++) dense[i].frame = (uint32_t)(i / K);
+    check(zr_memcpy_async(lbox_.ptr, l.data(), l.size() * 4, 0, stream_));
+    check(zr_memcpy_async(fsize_.ptr, fs.data(), fs.size() * 4, 0, stream_));
+    check(zr_memcpy_async(due_views_.ptr, due.data(), n_ * sizeof(zr_view_desc), 0, stream_));
+    check(zr_memcpy_async(dense_views_.ptr, dense.data(), nv * sizeof(zr_view_desc), 0, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+// injected detections go ahead of the detector's result that this step consumes (test hook; the
+// order is the host HandTracker's and DeviceHandTracker's)
+void DeviceMultiTracker::apply_injected() {
+    bool any = false;
+    for (auto &v : injected_) any = any || !v.empty();
+    if (!any) return;
+    check(zr_stream_synchronize(stream_));
+    std::vector<int32_t> cnt(n_), pend(n_);
+    std::vector<float> d(n_ * dcap_ * 20, 0.f);
+    check(zr_memcpy_async(cnt.data(), count_.ptr, n_ * 4, 1, stream_));
+    check(zr_memcpy_async(pend.data(), det_pending_.ptr, n_ * 4, 1, stream_));
+    check(zr_memcpy_async(d.data(), dets_.ptr, d.size() * 4, 1, stream_));
+    check(zr_stream_synchronize(stream_));
+    for (size_t s = 0; s < n_; s++) {
+        if (injected_[s].empty()) continue;
+        std::vector<float> own;
+        const int no = pend[s] ? std::min(cnt[s], (int32_t)dcap_) : 0;
+        own.assign(d.begin() + s * dcap_ * 20, d.begin() + (s * dcap_ + no) * 20);
+        cnt[s] = 0;
+        pend[s] = 1;
+        for (const Detection &det : injected_[s]) {
+            if ((size_t)cnt[s] >= dcap_) break;
+            float *r = d.data() + (s * dcap_ + cnt[s]) * 20;
+            std::fill(r, r + 20, 0.f);
+            r[0] = det.confidence;
+            r[1] = det.angle;
+            r[2] = det.rect.center().x;
+            r[3] = det.rect.center().y;
+            r[4] = det.rect.width();
+            r[5] = det.rect.height();
+            cnt[s]++;
+        }
+        for (int k = 0; k < no && (size_t)cnt[s] < dcap_; k++, cnt[s]++)
+            std::copy(own.begin() + k * 20, own.begin() + (k + 1) * 20, d.begin() + (s * dcap_ + cnt[s]) * 20);
+        injected_[s].clear();
+    }
+    check(zr_memcpy_async(count_.ptr, cnt.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(det_pending_.ptr, pend.data(), n_ * 4, 0, stream_));
+    check(zr_memcpy_async(dets_.ptr, d.data(), d.size() * 4, 0, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms) {
+    if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
+    std::vector<zr_frame> zf(n_);
+    for (size_t i = 0; i < n_; i++) {
+        const Image &f = frames[i];
+        if (!f.on_device) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "tracker frames must be device-resident");
+        if (f.width != frames[0].width || f.height != frames[0].height)
+            throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "all streams share one frame size");
+        zf[i] = zr_frame{f.rgba, f.width, f.height, f.row_stride};
+    }
+    if (frames[0].width != fw_ || frames[0].height != fh_) frame_size(frames[0].width, frames[0].height);
+    apply_injected();
+    const size_t K = (size_t)cfg_.slots, nv = n_ * K;
+    const NeuralNetwork &ln = lm_->nn();
+    // 1. the previous step's estimates, each slot's found through that step's dense index
+    if (steps_ > 0) {
+        check(zr_track_update_indexed_async(state_.ptr, nv, &tcfg_, outs_[0].ptr, (size_t)ln.output_per_image(0),
+                                            outs_[1].ptr, (size_t)ln.output_per_image(1),
+                                            prev_compact_ ? dense_of_.ptr : nullptr, lm_out_.ptr, views_.ptr, stream_));
+        // 2. the head pose of the slots tracked just now, while pose, landmarks and state share a slot
+        if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, nv, (size_t)lm_net_.num_landmarks, stream_);
+    }
+    // 3. bookkeeping (tracking.rs:129-218)
+    check(zr_multi_manage_async(state_.ptr, ids_.ptr, roi_.ptr, src_.ptr, nobj_.ptr, next_id_.ptr, next_det_.ptr,
+                                det_pending_.ptr, count_.ptr, dets_.ptr, dcap_, fsize_.ptr, n_, &cfg_, now_ms,
+                                steps_ == 0 ? 1 : 0, views_.ptr, dropped_.ptr, stream_));
+    // 4.-5. the landmark network on the live slots' views of this frame
+    float *outs[4] = {outs_[0].ptr, outs_[1].ptr, outs_[2].ptr, outs_[3].ptr};
+    const ColorMapper lc = lm_->color_mapper();
+    if (compact_) {
+        check(zr_slot_compact_async(nobj_.ptr, n_, K, views_.ptr, dense_views_.ptr, dense_of_.ptr, nactive_.ptr,
+                                    lm_total_.ptr, stream_));
+        check(zr_cnn_estimate_device_views_count_async(ln.handle(), zf.data(), n_, dense_views_.ptr, nv, nactive_.ptr,
+                                                       lc.lo, lc.hi, outs, stream_));
+    } else {
+        check(zr_cnn_estimate_device_views_async(ln.handle(), zf.data(), n_, views_.ptr, nv, lc.lo, lc.hi, outs,
+                                                 stream_));
+        uncompacted_ += nv;
+    }
+    prev_compact_ = compact_;
+    // 6. the detector (Detector::detect_impl, detection.rs:224-267) on the streams step 3 asked to
+    // detect on, taken next step: their list and count stay on the device
+    float *dd[2] = {det_boxes_.ptr, det_logits_.ptr};
+    check(zr_due_compact_async(det_pending_.ptr, n_, &det_tmpl_, due_.ptr, ndue_.ptr, due_views_.ptr, due_total_.ptr,
+                               stream_));
+    const ColorMapper dc = det_->color_mapper();
+    check(zr_cnn_estimate_device_views_count_async(det_->nn().handle(), zf.data(), n_, due_views_.ptr, n_, ndue_.ptr,
+                                                   dc.lo, dc.hi, dd, stream_));
+    check(zr_detect_post_mapped_async(det_logits_.ptr, det_boxes_.ptr, anchors_.ptr, lbox_.ptr, n_, due_.ptr, ndue_.ptr,
+                                      &pcfg_, count_.ptr, dets_.ptr, dcap_, nullptr, stream_));
+    steps_++;
+}
+
+void DeviceMultiTracker::synchronize() {
+    if (stream_) check(zr_stream_synchronize(stream_));
+}
+
+std::vector<int32_t> DeviceMultiTracker::read_i32(const DeviceArray<int32_t> &a) {
+    std::vector<int32_t> h(n_);
+    check(zr_memcpy_async(h.data(), a.ptr, n_ * 4, 1, stream_));
+    synchronize();
+    return h;
+}
+
+uint64_t DeviceMultiTracker::read_u64(const DeviceArray<uint64_t> &a) {
+    uint64_t v = 0;
+    check(zr_memcpy_async(&v, a.ptr, 8, 1, stream_));
+    synchronize();
+    return v;
+}
+
+std::vector<int32_t> DeviceMultiTracker::object_counts() { return read_i32(nobj_); }
+std::vector<int32_t> DeviceMultiTracker::detection_pending() { return read_i32(det_pending_); }
+std::vector<int32_t> DeviceMultiTracker::dropped_objects() { return read_i32(dropped_); }
+
+std::vector<int32_t> DeviceMultiTracker::dropped_detections() {
+    std::vector<int32_t> h = read_i32(count_);
+    for (auto &c : h) c = c > (int32_t)dcap_ ? c - (int32_t)dcap_ : 0;
+    return h;
+}
+
+uint64_t DeviceMultiTracker::detector_frames() { return read_u64(due_total_); }
+uint64_t DeviceMultiTracker::landmark_images() { return read_u64(lm_total_) + uncompacted_; }
+
+std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {
+    if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
+    const int K = cfg_.slots, L = lm_net_.num_landmarks;
+    int32_t no = 0;
+    std::vector<uint64_t> ids(K);
+    std::vector<int32_t> src(K);
+    std::vector<float> roi(5 * K), lm((size_t)K * L * 3);
+    std::vector<zr_track_state> st(K);
+    std::vector<zr_pose> pose;
+    check(zr_memcpy_async(&no, nobj_.ptr + s, 4, 1, stream_));
+    check(zr_memcpy_async(ids.data(), ids_.ptr + s * K, 8 * K, 1, stream_));
+    check(zr_memcpy_async(src.data(), src_.ptr + s * K, 4 * K, 1, stream_));
+    check(zr_memcpy_async(roi.data(), roi_.ptr + s * K * 5, 20 * K, 1, stream_));
+    check(zr_memcpy_async(st.data(), state_.ptr + s * K, sizeof(zr_track_state) * K, 1, stream_));
+    check(zr_memcpy_async(lm.data(), lm_out_.ptr + (size_t)s * K * L * 3, lm.size() * 4, 1, stream_));
+    if (pose_.on() && pose_.ran && pose_.out.n >= n_ * (size_t)K) {
+        pose.resize(K);  // written per slot before the bookkeeping moved the objects: paired through src
+        check(zr_memcpy_async(pose.data(), pose_.out.ptr + s * K, sizeof(zr_pose) * K, 1, stream_));
+    }
+    synchronize();
+    std::vector<ObjectData> out;
+    for (int j = 0; j < no && j < K; j++) {
+        if (src[j] < 0 || src[j] >= K) continue;  // started this step: no result yet
+        ObjectData d;
+        d.id = ids[j];
+        d.landmarks.assign(lm.begin() + (size_t)src[j] * L * 3, lm.begin() + (size_t)(src[j] + 1) * L * 3);
+        d.view_rect = RotatedRect(Rect::from_center(roi[5 * j], roi[5 * j + 1], roi[5 * j + 2], roi[5 * j + 3]),
+                                  roi[5 * j + 4]);
+        d.confidence = st[j].confidence;
+        if (!pose.empty()) d.pose = pose[src[j]];
+        out.push_back(std::move(d));
+    }
+    return out;
+}
+
+}  // namespace zh

@@ -1,0 +1,114 @@
+// device_multi_tracker.h -- HandTracker's loop (crates/zaru/src/hand/tracking.rs:115-219)
+// generalised to any detector / landmark network pair, as the reference's TODO.txt asks
+// ("generalize HandTracker to allow tracking any type of object with a detector and landmarker
+// network"): K objects per video stream with stable ids, every object's state in HBM.  Each step
+// enqueues on one HIP stream, with no host decision between frames:
+//   1. the LandmarkTracker update of every slot from the previous step's estimate, found through
+//      the previous step's dense index (zr_track_update_indexed_async),
+//   2. with a pose reference set, the head pose of the slots that update tracked
+//      (zr_procrustes_analyze_tracked_async) -- before step 3 moves the states,
+//   3. the bookkeeping: lost objects leave, the previous step's detections are filtered against
+//      the objects' ROIs, new objects start, the swap_remove de-duplication, the redetection
+//      schedule (zr_multi_manage_async: zr_hand_manage_async's kernel),
+//   4. the live slots packed into a dense view table + device count (zr_slot_compact_async),
+//   5. the landmark network on exactly those views (zr_cnn_estimate_device_views_count_async),
+//   6. the detector on the streams step 3 asked to detect on, as DeviceHandTracker runs BlazePalm
+//      (zr_due_compact_async, the counted launches, zr_detect_post_mapped_async).
+// Schedule: a detection requested at step t is taken at step t + 1 (DeviceHandTracker's).
+// Face detectors start an object on the detection's bounding rect, unrotated and with the
+// LandmarkTracker's default padding (examples/facemesh.rs:49-54); the palm detector with
+// HandTracker's grow factor, angle and padding, which makes ("palm", "hand") DeviceHandTracker.
+#pragma once
+#include <memory>
+#include <optional>
+#include <vector>
+
+#include "detection.h"
+#include "device_tracker.h"
+#include "landmark.h"
+
+namespace zh {
+
+class DeviceMultiTracker {
+  public:
+    // any detector; a landmark network whose estimate has a confidence (FaceMesh V1 / V2, hand):
+    // the others are refused, as the reference's LandmarkTracker<E: Confidence> refuses them
+    DeviceMultiTracker(DetectorNetwork detector, LandmarkNetwork landmarker, size_t streams, int slots = 4,
+                       int device = 0);
+    ~DeviceMultiTracker();
+    DeviceMultiTracker(const DeviceMultiTracker &) = delete;
+    DeviceMultiTracker &operator=(const DeviceMultiTracker &) = delete;
+
+    void set_redetect_interval(double ms);
+    void set_iou_thresh(float t) { cfg_.iou_thresh = t; }
+    void set_loss_threshold(float t) { tcfg_.loss_thresh = t; }
+    void set_det_grow(float g);
+    void set_use_angle(bool on) { cfg_.use_angle = on ? 1 : 0; }
+    void set_roi_padding(float p);
+    // A/B switch (default on): off runs the landmark network on all streams x slots views each
+    // step, idle slots included (DeviceHandTracker's schedule).  The results are the same bits.
+    void set_compact(bool on) { compact_ = on; }
+    // head pose of every object against `points` (n x 3 floats, e.g. the canonical face mesh; empty:
+    // off, the default), as DeviceFaceLoop::set_pose_reference
+    void set_pose_reference(const std::vector<float> &points, bool flip_y = true);
+    // detections handed to stream s's next step as if its detector had produced them, ahead of the
+    // detector's own result (DeviceHandTracker::inject_detections)
+    void inject_detections(size_t s, const std::vector<Detection> &dets);
+    // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now()
+    void step(const std::vector<Image> &frames, double now_ms);
+    void synchronize();
+    size_t streams() const { return n_; }
+    int slots() const { return cfg_.slots; }
+    const LandmarkNetwork &landmarker() const { return lm_net_; }
+
+    struct ObjectData {
+        uint64_t id;
+        std::vector<float> landmarks;  // L x 3, frame px (the previous step's estimate)
+        RotatedRect view_rect;         // the object's ROI (HandData::view_rect)
+        float confidence;              // that estimate's Confidence::confidence
+        std::optional<zr_pose> pose;   // with a pose reference set
+    };
+    // after synchronize(): stream s's objects that have a result, in slot order
+    std::vector<ObjectData> objects(size_t s);
+    std::vector<int32_t> object_counts();      // every stream's objects, with a result or new
+    std::vector<int32_t> detection_pending();  // streams whose detection of the last step counts
+    std::vector<int32_t> dropped_objects();    // per stream: the last step's new objects that found no free slot
+    std::vector<int32_t> dropped_detections(); // per stream: detections past the detection capacity
+    size_t detection_capacity() const { return dcap_; }
+    uint64_t detector_frames();   // frames the detector ran on, summed over the steps
+    uint64_t landmark_images();   // views the landmark network ran on, summed over the steps
+
+  private:
+    void frame_size(uint32_t W, uint32_t H);
+    void apply_injected();
+    std::vector<int32_t> read_i32(const DeviceArray<int32_t> &a);
+    uint64_t read_u64(const DeviceArray<uint64_t> &a);
+    std::shared_ptr<const Cnn> det_, lm_;
+    DetectorNetwork det_net_;
+    LandmarkNetwork lm_net_;
+    zr_multi_cfg cfg_{};
+    zr_track_cfg tcfg_{};
+    zr_detpost_cfg pcfg_{};
+    size_t n_ = 0, dcap_ = 0;  // dcap_: every NMS output (the detector's anchor count)
+    uint64_t steps_ = 0;
+    void *stream_ = nullptr;
+    uint32_t fw_ = 0, fh_ = 0;
+    bool compact_ = true;
+    bool prev_compact_ = true;     // how the previous step stored its estimates
+    uint64_t uncompacted_ = 0;     // landmark images of the steps that ran with compaction off
+    DeviceArray<zr_track_state> state_;
+    DeviceArray<uint64_t> ids_, next_id_;
+    DeviceArray<uint32_t> fsize_;
+    DeviceArray<float> roi_, lm_out_, outs_[4], det_boxes_, det_logits_, anchors_, lbox_, dets_;
+    DeviceArray<int32_t> src_, nobj_, det_pending_, count_, dropped_;
+    DeviceArray<double> next_det_;
+    DeviceArray<zr_view_desc> views_, dense_views_, due_views_;
+    DeviceArray<int32_t> dense_of_, nactive_;  // slot -> image of the packed batch, and its size
+    DeviceArray<int32_t> due_, ndue_;
+    zr_view_desc det_tmpl_{};  // the letterboxed detector view (frame index set per stream)
+    DeviceArray<uint64_t> due_total_, lm_total_;
+    DevicePose pose_;
+    std::vector<std::vector<Detection>> injected_;
+};
+
+}  // namespace zh

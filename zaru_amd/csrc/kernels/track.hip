@@ -79,10 +79,15 @@ __global__ __launch_bounds__(256) void track_kernel(const TrackParams P) {
             if (tid == 0) P.state[i].tracked = 0;
             return;
         }
+        // the image of lm / flag that holds this ROI's estimate; read only now that the ROI is
+        // known to be active (an idle slot's entry is -1)
+        const int64_t img = P.index ? P.index[i] : i;
+        const bool held = img >= 0 && img < P.n;
         float conf = 1.f;
-        if (P.kind == 0) conf = sigmoid(P.flag[(int64_t)i * P.flag_stride]);  // num.rs:6-8
-        else if (P.kind == 1) conf = P.flag[(int64_t)i * P.flag_stride];
-        if (conf < P.loss_thresh) {
+        if (!held) conf = __builtin_nanf("");  // no estimate: lost, whatever the threshold
+        else if (P.kind == 0) conf = sigmoid(P.flag[img * P.flag_stride]);  // num.rs:6-8
+        else if (P.kind == 1) conf = P.flag[img * P.flag_stride];
+        if (!held || conf < P.loss_thresh) {
             invalidate_rows(P, i, tid);
             if (tid == 0) {
                 P.state[i].active = 0;
@@ -95,8 +100,8 @@ __global__ __launch_bounds__(256) void track_kernel(const TrackParams P) {
         // per-image landmark output 0 (lm_stride floats per image, checked on the host to hold
         // L x 3, 2L for kind 3, or the 71-point eye contour for kind 2, whose 5 iris points come
         // first from output 1, eye.rs:47-64)
-        const float *lm = P.lm + (int64_t)i * P.lm_stride;
-        const float *iris = P.kind == 2 && !P.pos ? P.flag + (int64_t)i * P.flag_stride : nullptr;
+        const float *lm = P.lm + img * P.lm_stride;
+        const float *iris = P.kind == 2 && !P.pos ? P.flag + img * P.flag_stride : nullptr;
         // already extracted (and filtered, lm_filter.hip) positions of this ROI, when given
         const float *pos = P.pos ? P.pos + (int64_t)i * L * 3 : nullptr;
         const float scale = st.local[2] / (float)P.in_w;
@@ -292,7 +297,7 @@ __global__ __launch_bounds__(64) void hand_manage_kernel(const HandManageParams 
             st.roi[1] = g.cy;
             st.roi[2] = g.w;
             st.roi[3] = g.h;
-            st.roi[4] = dd[1];
+            st.roi[4] = P.use_angle ? dd[1] : 0.f;
             st.active = 1;
             st.frame_w = P.fsize[2 * s];
             st.frame_h = P.fsize[2 * s + 1];
@@ -381,6 +386,50 @@ const char *launch_due_compact(const int32_t *det_pending, const TrackState *los
     hipLaunchKernelGGL(due_compact_kernel, dim3(1), dim3(1024), 0, s, det_pending, lost_of, S, tmpl, due, ndue,
                        due_views, total);
     return "due_compact_kernel";
+}
+
+// one workgroup: a block-wide exclusive scan of the streams' object counts per 1024-stream chunk
+// (an inclusive wave scan by shuffles, the 16 wave sums through LDS); each thread then walks its
+// stream's K slots
+__global__ __launch_bounds__(1024) void slot_compact_kernel(const SlotCompactParams P) {
+    __shared__ int wsum[16];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int base = 0;
+    for (int64_t c0 = 0; c0 < P.S; c0 += 1024) {  // (64-bit: S may be within 1024 of 2^31)
+        const int64_t s = c0 + t;
+        const int c = s < P.S ? min(max(P.counts[s], 0), P.K) : 0;
+        int inc = c;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int i = 0; i < 16; ++i) {
+            before += i < w ? wsum[i] : 0;
+            total += wsum[i];
+        }
+        if (s < P.S) {
+            const int64_t slot0 = s * P.K;
+            const int k0 = base + before + (inc - c);
+            for (int h = 0; h < P.K; ++h) {
+                if (h < c) P.dense_views[k0 + h] = P.views[slot0 + h];
+                P.dense_of[slot0 + h] = h < c ? k0 + h : -1;
+            }
+        }
+        base += total;
+        __syncthreads();  // wsum is rewritten by the next chunk
+    }
+    if (t == 0) {
+        *P.nactive = base;
+        if (P.total) *P.total += (uint64_t)base;
+    }
+}
+
+const char *launch_slot_compact(const SlotCompactParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(slot_compact_kernel, dim3(1), dim3(1024), 0, s, p);
+    return "slot_compact_kernel";
 }
 
 // Rust's f32::total_cmp key (TotalF32, num.rs): the bits with the magnitude flipped for negatives,

@@ -77,6 +77,7 @@ struct Ctx {
     std::mutex mu;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
+    hipStream_t done_on = nullptr;  // the caller's stream `done` was last recorded on (forget_stream)
     float *arena = nullptr;
     size_t arena_floats = 0;
     float *input = nullptr;  // network input staging
@@ -184,6 +185,18 @@ struct Profiler final : zr::LaunchHook {
 
 }  // namespace
 
+// every live session, so zr_stream_destroy can find the contexts whose `done` event was last
+// recorded on the stream that goes (forget_stream below); never destroyed, so sessions and streams
+// that go at process exit still find it
+struct SessionRegistry {
+    std::mutex mu;
+    std::vector<zr_session *> live;
+};
+static SessionRegistry &sessions() {
+    static SessionRegistry *r = new SessionRegistry;
+    return *r;
+}
+
 struct zr_session {
     Profiler prof;
     int device = 0;
@@ -200,10 +213,14 @@ struct zr_session {
         for (size_t i = 0; i < pool.size(); i++) {
             Ctx *c = pool[(next + i) % pool.size()].get();
             if (c->mu.try_lock()) {
-                if (hipEventQuery(c->done) == hipSuccess) {
+                const hipError_t q = hipEventQuery(c->done);
+                if (q == hipSuccess) {
                     next = (next + i + 1) % pool.size();
                     return c;
                 }
+                // busy (or not queryable): another context serves; the query's status is handled
+                // here and must not surface at a later launch check
+                if (q != hipErrorNotReady) (void)hipGetLastError();
                 c->mu.unlock();
             }
         }
@@ -224,11 +241,46 @@ struct zr_session {
         return c;
     }
 
+    zr_session() {
+        SessionRegistry &r = sessions();
+        std::lock_guard<std::mutex> g(r.mu);
+        r.live.push_back(this);
+    }
     ~zr_session() {
+        {
+            SessionRegistry &r = sessions();
+            std::lock_guard<std::mutex> g(r.mu);
+            r.live.erase(std::remove(r.live.begin(), r.live.end(), this), r.live.end());
+        }
         pool.clear();
         (void)hipFree(weights);
     }
 };
+
+// A context's `done` event remembers the stream it was recorded on, and the HIP runtime looks at
+// that stream again when the event is queried or waited for.  Sessions outlive their callers'
+// streams (one process-wide session per network, a stream per tracker), so before a stream is
+// destroyed every event last recorded on it is replaced by a fresh, never recorded one (which
+// queries as complete) once its work has finished.
+static void forget_stream(hipStream_t stream) {
+    if (!stream) return;
+    SessionRegistry &r = sessions();
+    std::lock_guard<std::mutex> g(r.mu);
+    for (zr_session *s : r.live) {
+        std::lock_guard<std::mutex> pl(s->pool_mu);
+        for (auto &c : s->pool) {
+            std::lock_guard<std::mutex> cl(c->mu);
+            if (c->done_on != stream || !c->done) continue;
+            (void)hipEventSynchronize(c->done);
+            hipEvent_t fresh = nullptr;
+            if (hipEventCreateWithFlags(&fresh, hipEventDisableTiming) == hipSuccess) {
+                (void)hipEventDestroy(c->done);
+                c->done = fresh;
+            }
+            c->done_on = nullptr;
+        }
+    }
+}
 
 namespace {
 
@@ -272,6 +324,7 @@ int enqueue(zr_session *s, Ctx *c, int N, const float *input, int64_t in_sN, int
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->done, stream));
+    c->done_on = stream;
     return ZR_OK;
 }
 
@@ -671,9 +724,9 @@ int zr_track_seed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *c
     });
 }
 
-int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg, const float *d_landmarks,
-                          size_t lm_stride, const float *d_flag, size_t flag_stride, float *d_lm_out,
-                          zr_view_desc *d_views, void *hip_stream) {
+static int track_update(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg, const float *d_landmarks,
+                        size_t lm_stride, const float *d_flag, size_t flag_stride, const int32_t *d_index,
+                        float *d_lm_out, zr_view_desc *d_views, void *hip_stream) {
     return guarded([&]() -> int {
         zr::TrackParams p{};
         if (int rc = track_params(p, d_state, n, cfg, d_views)) return rc;
@@ -682,11 +735,27 @@ int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg 
         p.lm_stride = (int)lm_stride;
         p.flag = d_flag;
         p.flag_stride = (int)flag_stride;
+        p.index = d_index;
         p.lm_out = d_lm_out;
         zr::launch_track(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
+}
+
+int zr_track_update_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg, const float *d_landmarks,
+                          size_t lm_stride, const float *d_flag, size_t flag_stride, float *d_lm_out,
+                          zr_view_desc *d_views, void *hip_stream) {
+    return track_update(d_state, n, cfg, d_landmarks, lm_stride, d_flag, flag_stride, nullptr, d_lm_out, d_views,
+                        hip_stream);
+}
+
+int zr_track_update_indexed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                  const float *d_landmarks, size_t lm_stride, const float *d_flag,
+                                  size_t flag_stride, const int32_t *d_index, float *d_lm_out,
+                                  zr_view_desc *d_views, void *hip_stream) {
+    return track_update(d_state, n, cfg, d_landmarks, lm_stride, d_flag, flag_stride, d_index, d_lm_out, d_views,
+                        hip_stream);
 }
 
 int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
@@ -961,19 +1030,21 @@ int zr_track_seed_detections_async(const int32_t *d_count, const float *d_dets, 
     });
 }
 
-int zr_hand_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_hroi, int32_t *d_src, int32_t *d_nhands,
-                         uint64_t *d_next_id, double *d_next_det, int32_t *d_det_pending, const int32_t *d_count,
-                         const float *d_dets, size_t dcap, const uint32_t *d_frame_size, size_t n,
-                         const zr_hand_cfg *cfg, double now_ms, int init_clock, zr_view_desc *d_views,
-                         int32_t *d_dropped, void *hip_stream) {
+// zr_hand_manage_async and zr_multi_manage_async: one kernel, the hand tracker's configuration being
+// the multi-object one with the detection's angle always used
+static int manage_impl(zr_track_state *d_state, uint64_t *d_ids, float *d_hroi, int32_t *d_src, int32_t *d_nhands,
+                       uint64_t *d_next_id, double *d_next_det, int32_t *d_det_pending, const int32_t *d_count,
+                       const float *d_dets, size_t dcap, const uint32_t *d_frame_size, size_t n,
+                       const zr_multi_cfg *cfg, double now_ms, int init_clock, zr_view_desc *d_views,
+                       int32_t *d_dropped, void *hip_stream) {
     return guarded([&]() -> int {
         if (!d_state || !d_ids || !d_hroi || !d_src || !d_nhands || !d_next_id || !d_next_det || !d_det_pending ||
             !d_count || !d_dets || !d_frame_size || !cfg || !d_views)
             return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
         if (n == 0) return ZR_OK;
         if (cfg->slots <= 0 || cfg->slots > 64 || dcap == 0 || dcap > 65536 || (uint64_t)n * cfg->slots > (1u << 24) ||
-            cfg->aspect_w <= 0 || cfg->aspect_h <= 0 || !(cfg->interval_ms >= 0.0) || !(cfg->palm_grow >= 0.f))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "bad hand tracker configuration");
+            cfg->aspect_w <= 0 || cfg->aspect_h <= 0 || !(cfg->interval_ms >= 0.0) || !(cfg->det_grow >= 0.f))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "bad tracker bookkeeping configuration");
         zr::HandManageParams p{};
         p.state = reinterpret_cast<zr::TrackState *>(d_state);
         p.ids = d_ids;
@@ -992,13 +1063,67 @@ int zr_hand_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_hroi
         p.H = cfg->slots;
         p.dcap = (int)dcap;
         p.iou = cfg->iou_thresh;
-        p.grow = cfg->palm_grow;
+        p.grow = cfg->det_grow;
         p.now = now_ms;
         p.interval = cfg->interval_ms;
         p.init_clock = init_clock ? 1 : 0;
         p.asp_w = cfg->aspect_w;
         p.asp_h = cfg->aspect_h;
+        p.use_angle = cfg->use_angle ? 1 : 0;
         zr::launch_hand_manage(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_hand_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_hroi, int32_t *d_src, int32_t *d_nhands,
+                         uint64_t *d_next_id, double *d_next_det, int32_t *d_det_pending, const int32_t *d_count,
+                         const float *d_dets, size_t dcap, const uint32_t *d_frame_size, size_t n,
+                         const zr_hand_cfg *cfg, double now_ms, int init_clock, zr_view_desc *d_views,
+                         int32_t *d_dropped, void *hip_stream) {
+    zr_multi_cfg m{};
+    if (cfg) {
+        m.slots = cfg->slots;
+        m.iou_thresh = cfg->iou_thresh;
+        m.det_grow = cfg->palm_grow;
+        m.use_angle = 1;  // tracking.rs:159
+        m.interval_ms = cfg->interval_ms;
+        m.aspect_w = cfg->aspect_w;
+        m.aspect_h = cfg->aspect_h;
+    }
+    return manage_impl(d_state, d_ids, d_hroi, d_src, d_nhands, d_next_id, d_next_det, d_det_pending, d_count, d_dets,
+                       dcap, d_frame_size, n, cfg ? &m : nullptr, now_ms, init_clock, d_views, d_dropped, hip_stream);
+}
+
+int zr_multi_manage_async(zr_track_state *d_state, uint64_t *d_ids, float *d_roi, int32_t *d_src, int32_t *d_nobjects,
+                          uint64_t *d_next_id, double *d_next_det, int32_t *d_det_pending, const int32_t *d_count,
+                          const float *d_dets, size_t dcap, const uint32_t *d_frame_size, size_t n,
+                          const zr_multi_cfg *cfg, double now_ms, int init_clock, zr_view_desc *d_views,
+                          int32_t *d_dropped, void *hip_stream) {
+    return manage_impl(d_state, d_ids, d_roi, d_src, d_nobjects, d_next_id, d_next_det, d_det_pending, d_count, d_dets,
+                       dcap, d_frame_size, n, cfg, now_ms, init_clock, d_views, d_dropped, hip_stream);
+}
+
+int zr_slot_compact_async(const int32_t *d_counts, size_t n_streams, size_t slots, const zr_view_desc *d_views,
+                          zr_view_desc *d_dense_views, int32_t *d_dense_of, int32_t *d_nactive, uint64_t *d_total,
+                          void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_counts || !d_views || !d_dense_views || !d_dense_of || !d_nactive)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n_streams == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "no streams");
+        if (slots == 0 || slots > 64) return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64");
+        if (n_streams > (size_t)INT32_MAX / slots)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "streams x slots beyond the kernel's 32-bit slot index");
+        zr::SlotCompactParams p{};
+        p.counts = d_counts;
+        p.views = reinterpret_cast<const zr::ViewDesc *>(d_views);
+        p.dense_views = reinterpret_cast<zr::ViewDesc *>(d_dense_views);
+        p.dense_of = d_dense_of;
+        p.nactive = d_nactive;
+        p.total = d_total;
+        p.S = (int)n_streams;
+        p.K = (int)slots;
+        zr::launch_slot_compact(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
@@ -1403,6 +1528,7 @@ int zr_stream_create(void **stream) {
 
 int zr_stream_destroy(void *stream) {
     return guarded([&]() -> int {
+        forget_stream((hipStream_t)stream);
         HIP_TRY(hipStreamDestroy((hipStream_t)stream));
         return ZR_OK;
     });

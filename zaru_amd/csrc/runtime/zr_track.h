@@ -39,6 +39,9 @@ struct TrackParams {
     int rpf;               // ROIs per frame: ROI i samples frame i / rpf
     const float *pos;      // null, or the already extracted positions (n x L x 3, network px:
                            // lm_filter.hip) the map-out reads instead of extracting from lm / flag
+    const int32_t *index;  // null (ROI i reads image i of lm / flag), or per ROI the image that holds its
+                           // estimate (slot_compact's dense_of); read for active ROIs only, and an
+                           // active ROI whose index is outside [0, n) counts as lost
 };
 
 const char *launch_track(const TrackParams &p, hipStream_t s);
@@ -151,8 +154,23 @@ struct HandManageParams {
     double now, interval;
     int init_clock;          // 1: next_det = now first (the reference starts the clock at construction)
     int asp_w, asp_h;
+    int use_angle;           // a started object's ROI angle: 1 the detection's (hands), 0 none (faces)
 };
 const char *launch_hand_manage(const HandManageParams &p, hipStream_t s);
+// The live slots of every stream after hand_manage (stream s: [s * K, s * K + counts[s])) packed
+// in stream-then-slot order: dense_views[k] = views[slot], dense_of[slot] = k (idle slots: -1),
+// *nactive = their number, *total += it (total may be null).  One workgroup, an exclusive scan of
+// the per-stream counts per 1024-stream chunk, so the order never depends on scheduling.
+struct SlotCompactParams {
+    const int32_t *counts;   // [S] (hand_manage's nhands; clamped to 0..K)
+    const ViewDesc *views;   // [S * K]
+    ViewDesc *dense_views;   // [S * K] out: the first *nactive entries
+    int32_t *dense_of;       // [S * K] out
+    int32_t *nactive;        // out
+    uint64_t *total;         // in / out, may be null
+    int S, K;
+};
+const char *launch_slot_compact(const SlotCompactParams &p, hipStream_t s);
 // The streams whose detection hand_manage requested (det_pending[s] != 0), or -- lost_of != null
 // -- whose tracker state holds no RoI (active == 0), in stream order: due[k] = s for k < *ndue,
 // and due_views[k] = the template view with frame = s (one workgroup).

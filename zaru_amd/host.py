@@ -5,6 +5,14 @@ Names follow the reference: ``Detector`` (crates/zaru/src/detection.rs), ``NonMa
 (detection/nms.rs), ``Estimator`` / ``LandmarkTracker`` (landmark.rs), ``Rect`` /
 ``RotatedRect`` (zaru-image/src/rect.rs), plus the batched ``DetectTrackPipeline`` that runs a
 whole batch of device-resident frames through detect -> track.
+
+Video loops with their state on the device: ``DeviceTracker``, ``DeviceFaceLoop`` (one face per
+stream), ``DeviceHandTracker`` and ``DeviceMultiTracker(detector="face", landmarker="facemesh",
+streams=1, slots=4, device=0)``: K objects per stream with stable ids for any detector
+(``face``, ``face_full``, ``palm``) and any landmark network with a confidence (``facemesh``,
+``facemesh_v2``, ``hand``).  ``step(frames, now_ms)`` enqueues only; after ``synchronize()``,
+``objects(s)`` lists ``{"id", "landmarks", "view_rect", "confidence"}`` (and ``"pose"`` with
+``set_pose_reference``) for stream ``s``, ``object_counts()`` every stream's objects.
 """
 from __future__ import annotations
 
