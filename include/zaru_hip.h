@@ -284,6 +284,40 @@ int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, cons
 int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
                                     const float *d_positions, const float *d_flag, size_t flag_stride,
                                     float *d_lm_out, zr_view_desc *d_views, void *hip_stream);
+/* The two calls above for a loop whose objects move between slots (zr_multi_manage_async): a
+ * filter's state belongs to an object, so it follows the object.  The n = streams x slots rows are
+ * ROIs in slot order, stream s owning rows [s * slots, s * slots + slots).  For row i:
+ *   - the estimate is read at image d_index[i] (zr_slot_compact_async's d_dense_of, as
+ *     zr_track_update_indexed_async reads it; d_index == NULL: image i);
+ *   - the incoming state is row (i / slots) * slots + d_src[i] of d_filter_state_in, d_src being
+ *     zr_multi_manage_async's d_src of the step that stored the estimates: the slot, within the
+ *     stream, the object held when the previous call wrote its state.  A d_src[i] outside
+ *     [0, slots) is a new object: it starts from the default (all-zero) state, whatever a previous
+ *     occupant of the slot left behind, so its first estimate passes through and primes it;
+ *   - the new state is written to row i of d_filter_state_out and the positions to row i of
+ *     d_positions.
+ * A row with nothing to filter -- d_state[i].active == 0, or active with d_index[i] outside [0, n)
+ * (no estimate: the update will call it lost) -- gets a NaN d_positions row and an all-zero output
+ * state row.  Every row of d_filter_state_out is written by every call, and d_filter_state_in is
+ * only read: the two are distinct buffers of n x zr_lm_filter_state_size bytes that swap roles
+ * after each call.  The same checks as zr_lm_filter_async, and ZR_ERR_INVALID_ARGUMENT for
+ * d_state == NULL, d_src == NULL, slots outside 1..64, n not a multiple of slots and, with a filter
+ * set, a NULL state buffer or d_filter_state_in == d_filter_state_out.  ZR_LM_FILTER_NONE only
+ * extracts (both state buffers may be NULL).  Same arithmetic, bit for bit. */
+int zr_lm_filter_indexed_async(const zr_lm_filter *filter, const zr_track_cfg *cfg,
+                               const zr_track_state *d_state, size_t n, size_t slots,
+                               const float *d_landmarks, size_t lm_stride, const float *d_flag,
+                               size_t flag_stride, const int32_t *d_index, const int32_t *d_src,
+                               float elapsed_s, const void *d_filter_state_in, void *d_filter_state_out,
+                               float *d_positions, void *hip_stream);
+/* zr_track_update_positions_async when the estimates are not stored in ROI order: d_positions is
+ * by ROI (what zr_lm_filter_indexed_async wrote), the flag of ROI i is read at image d_index[i],
+ * and an active ROI whose index is outside [0, n) is lost (zr_track_update_indexed_async's rules).
+ * d_index == NULL is the plain call. */
+int zr_track_update_positions_indexed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                            const float *d_positions, const float *d_flag,
+                                            size_t flag_stride, const int32_t *d_index, float *d_lm_out,
+                                            zr_view_desc *d_views, void *hip_stream);
 
 /* ---- Head pose: Procrustes analysis of landmark sets (crates/zaru/src/procrustes.rs) ---------
  * ProcrustesAnalyzer on the device: the similarity transform (scale, rotation, translation) that

@@ -102,6 +102,8 @@ SIGNATURES = [
     ("zr_lm_filter_state_size", _I, [_P, _SZ, C.POINTER(_SZ)]),
     ("zr_lm_filter_async", _I, [_P, _P, _P, _SZ, _P, _SZ, _P, _SZ, _F, _P, _P, _P]),
     ("zr_track_update_positions_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P]),
+    ("zr_lm_filter_indexed_async", _I, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _P, _F, _P, _P, _P, _P]),
+    ("zr_track_update_positions_indexed_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     ("zr_procrustes_create", _I, [_P, _SZ, C.POINTER(_P)]),
     ("zr_procrustes_destroy", None, [_P]),
     ("zr_procrustes_analyze_async", _I, [_P, _P, _SZ, _SZ, _I, _P, _P, _P]),

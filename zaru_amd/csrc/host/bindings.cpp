@@ -488,18 +488,20 @@ PYBIND11_MODULE(_zaru_host, m) {
         }, py::arg("points"), py::arg("flip_y") = true)
         .def("inject_detections", &DeviceMultiTracker::inject_detections)
         .def("step", [](DeviceMultiTracker &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
-                        double now_ms) {
+                        double now_ms, std::optional<float> elapsed) {
             const std::vector<Image> im = device_frames(frames);
             py::gil_scoped_release nogil;
-            t.step(im, now_ms);
-        }, py::arg("frames"), py::arg("now_ms"))
+            t.step(im, now_ms, elapsed);
+        }, py::arg("frames"), py::arg("now_ms"), py::arg("elapsed") = py::none())
         // frames given as host arrays are refused by step (test hook for that rejection)
         .def("step_host", [](DeviceMultiTracker &t, const std::vector<py::array_t<uint8_t, py::array::c_style>> &frames,
-                             double now_ms) {
+                             double now_ms, std::optional<float> elapsed) {
             std::vector<Image> im;
             for (auto &f : frames) im.push_back(host_image(f));
-            t.step(im, now_ms);
-        }, py::arg("frames"), py::arg("now_ms"))
+            t.step(im, now_ms, elapsed);
+        }, py::arg("frames"), py::arg("now_ms"), py::arg("elapsed") = py::none())
+        .def("set_filter", [](DeviceMultiTracker &t, const py::object &f, float dt) { t.set_filter(filter_arg(f), dt); },
+             py::arg("filter"), py::arg("dt") = Estimator::DEFAULT_FILTER_DT)
         .def("synchronize", &DeviceMultiTracker::synchronize, py::call_guard<py::gil_scoped_release>())
         .def("__len__", &DeviceMultiTracker::streams)
         .def("slots", &DeviceMultiTracker::slots)

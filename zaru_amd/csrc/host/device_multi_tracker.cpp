@@ -2,6 +2,7 @@
 #include "device_multi_tracker.h"
 
 #include <algorithm>
+#include <cmath>
 
 #include "hand_tracker.h"
 
@@ -127,6 +128,13 @@ void DeviceMultiTracker::set_pose_reference(const std::vector<float> &points, bo
     pose_.set(points, flip_y, (size_t)lm_net_.num_landmarks, stream_);
 }
 
+void DeviceMultiTracker::set_filter(const std::optional<FilterParams> &f, float dt) {
+    filter_.two = true;
+    filter_.set(f, dt, (size_t)lm_net_.num_landmarks, n_ * (size_t)cfg_.slots, stream_);
+    // the last step's elapsed stays with its estimates unless the new filter could not take it
+    if (prev_elapsed_ && !(std::isfinite(*prev_elapsed_) && *prev_elapsed_ > 0.f)) prev_elapsed_.reset();
+}
+
 void DeviceMultiTracker::inject_detections(size_t s, const std::vector<Detection> &dets) {
     if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
     for (const Detection &d : dets) injected_[s].push_back(d);
@@ -205,8 +213,15 @@ void DeviceMultiTracker::apply_injected() {
     check(zr_stream_synchronize(stream_));
 }
 
-void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms) {
+void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
+    // both checked before anything is enqueued: this frame's elapsed, and the previous frame's that
+    // this step filters with
+    float el = 0.f;
+    if (filter_.on()) {
+        (void)filter_.elapsed(elapsed);
+        el = filter_.elapsed(prev_elapsed_);
+    }
     std::vector<zr_frame> zf(n_);
     for (size_t i = 0; i < n_; i++) {
         const Image &f = frames[i];
@@ -221,9 +236,24 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms) {
     const NeuralNetwork &ln = lm_->nn();
     // 1. the previous step's estimates, each slot's found through that step's dense index
     if (steps_ > 0) {
-        check(zr_track_update_indexed_async(state_.ptr, nv, &tcfg_, outs_[0].ptr, (size_t)ln.output_per_image(0),
-                                            outs_[1].ptr, (size_t)ln.output_per_image(1),
-                                            prev_compact_ ? dense_of_.ptr : nullptr, lm_out_.ptr, views_.ptr, stream_));
+        const int32_t *index = prev_compact_ ? dense_of_.ptr : nullptr;
+        if (filter_.on()) {
+            // each slot's state comes from the slot its object held when the last filtered step wrote
+            // it (src_, the previous step's bookkeeping), a new object's is the default; the RoI and
+            // the pose follow the filtered landmarks
+            check(zr_lm_filter_indexed_async(&filter_.f, &tcfg_, state_.ptr, nv, K, outs_[0].ptr,
+                                             (size_t)ln.output_per_image(0), outs_[1].ptr,
+                                             (size_t)ln.output_per_image(1), index, src_.ptr, el, filter_.state_in(),
+                                             filter_.state_out(), filter_.pos.ptr, stream_));
+            filter_.flipped = !filter_.flipped;
+            check(zr_track_update_positions_indexed_async(state_.ptr, nv, &tcfg_, filter_.pos.ptr, outs_[1].ptr,
+                                                          (size_t)ln.output_per_image(1), index, lm_out_.ptr,
+                                                          views_.ptr, stream_));
+        } else {
+            check(zr_track_update_indexed_async(state_.ptr, nv, &tcfg_, outs_[0].ptr, (size_t)ln.output_per_image(0),
+                                                outs_[1].ptr, (size_t)ln.output_per_image(1), index, lm_out_.ptr,
+                                                views_.ptr, stream_));
+        }
         // 2. the head pose of the slots tracked just now, while pose, landmarks and state share a slot
         if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, nv, (size_t)lm_net_.num_landmarks, stream_);
     }
@@ -245,6 +275,7 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms) {
         uncompacted_ += nv;
     }
     prev_compact_ = compact_;
+    prev_elapsed_ = filter_.on() ? elapsed : std::nullopt;
     // 6. the detector (Detector::detect_impl, detection.rs:224-267) on the streams step 3 asked to
     // detect on, taken next step: their list and count stay on the device
     float *dd[2] = {det_boxes_.ptr, det_logits_.ptr};

@@ -4,7 +4,10 @@
 // network"): K objects per video stream with stable ids, every object's state in HBM.  Each step
 // enqueues on one HIP stream, with no host decision between frames:
 //   1. the LandmarkTracker update of every slot from the previous step's estimate, found through
-//      the previous step's dense index (zr_track_update_indexed_async),
+//      the previous step's dense index (zr_track_update_indexed_async); with a landmark filter set
+//      (set_filter) zr_lm_filter_indexed_async first -- each slot's filter state gathered from the
+//      slot its object held before the previous step's bookkeeping moved it -- and the update on
+//      the filtered positions (zr_track_update_positions_indexed_async),
 //   2. with a pose reference set, the head pose of the slots that update tracked
 //      (zr_procrustes_analyze_tracked_async) -- before step 3 moves the states,
 //   3. the bookkeeping: lost objects leave, the previous step's detections are filtered against
@@ -54,8 +57,16 @@ class DeviceMultiTracker {
     // detections handed to stream s's next step as if its detector had produced them, ahead of the
     // detector's own result (DeviceHandTracker::inject_detections)
     void inject_detections(size_t s, const std::vector<Detection> &dets);
-    // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now()
-    void step(const std::vector<Image> &frames, double now_ms);
+    // Estimator::set_filter for every object (nullopt: none, the default): each object owns a fresh
+    // copy of the filter from the step it starts until it leaves (the reference's HandTracker builds
+    // one Estimator per object, hand/tracking.rs:63,160), its state following it from slot to slot.
+    // Replaces the filter and resets every object's state.
+    void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
+    // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now().
+    // With a filter set: `elapsed` seconds between the previous frame and this one (default: the
+    // filter's dt), one value for all objects, independent of now_ms.  It belongs to this frame's
+    // estimates, which the next step filters and consumes.
+    void step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed = std::nullopt);
     void synchronize();
     size_t streams() const { return n_; }
     int slots() const { return cfg_.slots; }
@@ -108,6 +119,8 @@ class DeviceMultiTracker {
     zr_view_desc det_tmpl_{};  // the letterboxed detector view (frame index set per stream)
     DeviceArray<uint64_t> due_total_, lm_total_;
     DevicePose pose_;
+    DeviceFilter filter_;                 // two state buffers of streams x slots rows
+    std::optional<float> prev_elapsed_;   // the previous step's `elapsed`: its estimates' (nullopt: dt)
     std::vector<std::vector<Detection>> injected_;
 };
 

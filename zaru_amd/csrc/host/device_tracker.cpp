@@ -36,6 +36,12 @@ void DeviceFilter::reset(size_t num_landmarks, size_t n, void *stream) {
     state.resize(bytes * n);
     pos.resize(n * num_landmarks * 3);
     check(zr_memset_async(state.ptr, 0, bytes * n, stream));  // all-zero: no value seen
+    if (two) {
+        if (bytes * n > back.n) check(zr_stream_synchronize(stream));
+        back.resize(bytes * n);
+        check(zr_memset_async(back.ptr, 0, bytes * n, stream));
+        flipped = false;
+    }
 }
 
 float DeviceFilter::elapsed(const std::optional<float> &e) const {

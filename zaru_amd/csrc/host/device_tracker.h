@@ -26,6 +26,13 @@ struct DeviceFilter {
     size_t streams = 0;  // the stream count the state holds
     DeviceArray<uint8_t> state;
     DeviceArray<float> pos;
+    // a loop whose objects move between slots (DeviceMultiTracker) filters from one state buffer
+    // into another (zr_lm_filter_indexed_async): `two` sizes and resets `back` with `state`, and
+    // `flipped` says that `back` holds the current state (the loop flips it after a filtered step)
+    bool two = false, flipped = false;
+    DeviceArray<uint8_t> back;
+    uint8_t *state_in() const { return flipped ? back.ptr : state.ptr; }
+    uint8_t *state_out() const { return flipped ? state.ptr : back.ptr; }
     bool on() const { return f.kind != ZR_LM_FILTER_NONE; }
     // replace the filter; `streams` (may be 0: sized later) default states, zeroed on `stream`
     void set(const std::optional<FilterParams> &p, float dt, size_t num_landmarks, size_t streams, void *stream);

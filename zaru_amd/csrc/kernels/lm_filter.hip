@@ -25,6 +25,37 @@ __device__ __forceinline__ float exponential_smoothing(float a, float x, float x
     return a * x + (1.f - a) * x_prev;
 }
 
+// One primed value's step: the filtered value (also the new x of the state), `v` updated in place
+// (alpha-beta v / 1 euro prev.dx; EMA leaves it).  Shared by both kernels, so they agree bit for bit.
+__device__ __forceinline__ float filter_primed(const LmFilterParams &P, float x, float sx, float &v) {
+    if (P.filter == 1) return P.p0 * x + (1.f - P.p0) * sx;  // ema.rs:41
+    if (P.filter == 2) {  // alpha_beta.rs:52-58
+        const float prediction = sx + v * P.elapsed;
+        const float residual = x - prediction;
+        v = v + P.p1 * residual / P.elapsed;
+        return prediction + P.p0 * residual;
+    }
+    // one_euro.rs:74-85
+    const float a_d = smoothing_factor(P.elapsed, P.p2);
+    const float dx = (x - sx) / P.elapsed;
+    const float dx_hat = exponential_smoothing(a_d, dx, v);
+    const float cutoff = P.p0 + P.p1 * __builtin_fabsf(dx_hat);
+    const float a = smoothing_factor(P.elapsed, cutoff);
+    v = dx_hat;
+    return exponential_smoothing(a, x, sx);
+}
+
+// the kind's extract of value v of image `img`, as track_kernel's `mapped` before the scale
+__device__ __forceinline__ float extract_value(const LmFilterParams &P, int64_t img, int v) {
+    if (P.kind == 3) {  // multipie68.rs:71-80: relative (x, y) * input resolution, z = 0
+        const int j = v / 3, c = v - 3 * j;
+        return c == 2 ? 0.f : P.lm[img * P.lm_stride + 2 * j + c] * (float)(c == 0 ? P.in_w : P.in_h);
+    }
+    if (P.kind == 2)  // eye.rs:47-64: 5 iris points (output 1), then the contour
+        return v < 15 ? P.flag[img * P.flag_stride + v] : P.lm[img * P.lm_stride + (v - 15)];
+    return P.lm[img * P.lm_stride + v];
+}
+
 __global__ __launch_bounds__(256) void lm_filter_kernel(const LmFilterParams P, int chunks) {
     const int i = blockIdx.x / chunks;  // stream
     const int nv = 3 * P.L;
@@ -35,50 +66,89 @@ __global__ __launch_bounds__(256) void lm_filter_kernel(const LmFilterParams P, 
         *out = __builtin_nanf("");
         return;
     }
-    // the kind's extract, as track_kernel's `mapped` before the scale
-    float x;
-    if (P.kind == 3) {  // multipie68.rs:71-80: relative (x, y) * input resolution, z = 0
-        const int j = v / 3, c = v - 3 * j;
-        x = c == 2 ? 0.f : P.lm[(int64_t)i * P.lm_stride + 2 * j + c] * (float)(c == 0 ? P.in_w : P.in_h);
-    } else if (P.kind == 2) {  // eye.rs:47-64: 5 iris points (output 1), then the contour
-        x = v < 15 ? P.flag[(int64_t)i * P.flag_stride + v] : P.lm[(int64_t)i * P.lm_stride + (v - 15)];
-    } else {
-        x = P.lm[(int64_t)i * P.lm_stride + v];
-    }
+    float x = extract_value(P, i, v);
     if (P.filter != 0) {
         uint32_t *primed = P.fstate + (int64_t)i * (P.filter == 1 ? 2 : 3) * nv + v;
         float *sx = reinterpret_cast<float *>(primed + nv);
         if (!*primed) {  // the first value passes through and primes the state (v / dx stay 0)
             *primed = 1u;
             *sx = x;
-        } else if (P.filter == 1) {  // ema.rs:41
-            x = P.p0 * x + (1.f - P.p0) * *sx;
-            *sx = x;
-        } else if (P.filter == 2) {  // alpha_beta.rs:52-58
+        } else if (P.filter == 1) {
+            float unused = 0.f;
+            *sx = x = filter_primed(P, x, *sx, unused);
+        } else {
             float *sv = sx + nv;
-            const float vel = *sv;
-            const float prediction = *sx + vel * P.elapsed;
-            const float residual = x - prediction;
-            x = prediction + P.p0 * residual;
-            *sx = x;
-            *sv = vel + P.p1 * residual / P.elapsed;
-        } else {  // one_euro.rs:74-85
-            float *sv = sx + nv;
-            const float px = *sx;
-            const float a_d = smoothing_factor(P.elapsed, P.p2);
-            const float dx = (x - px) / P.elapsed;
-            const float dx_hat = exponential_smoothing(a_d, dx, *sv);
-            const float cutoff = P.p0 + P.p1 * __builtin_fabsf(dx_hat);
-            const float a = smoothing_factor(P.elapsed, cutoff);
-            x = exponential_smoothing(a, x, px);
-            *sx = x;
-            *sv = dx_hat;
+            float vel = *sv;
+            *sx = x = filter_primed(P, x, *sx, vel);
+            *sv = vel;
         }
     }
     *out = x;
 }
 
+// The multi-object loop's form (DeviceMultiTracker): a filter state belongs to an object, and the
+// bookkeeping (hand_manage_kernel) moves objects between the slots of their stream.  Row i's
+// estimate is image index[i] (slot_compact's dense_of; null: image i), its incoming state is row
+// src[i] of its stream in `fin` (hand_manage's src; outside [0, slots): a new object, the all-zero
+// default state), and its new state goes to row i of `fout`: the gather is fused, the state is
+// read and written once.  fin != fout, since a row is read by another workgroup than the one that
+// writes it.  Every row of fout and pos is written: a row with nothing to filter (not active, or
+// no estimate) gets the default state and NaN positions.  active, index[i] and src[i] are the
+// same for the whole workgroup (scalar loads); the state rows stay coalesced.
+__global__ __launch_bounds__(256) void lm_filter_indexed_kernel(const LmFilterParams P, int chunks, int slots,
+                                                                const int32_t *__restrict__ index,
+                                                                const int32_t *__restrict__ src,
+                                                                const uint32_t *__restrict__ fin,
+                                                                uint32_t *__restrict__ fout) {
+    const int i = blockIdx.x / chunks;  // row: stream i / slots, slot i % slots
+    const int nv = 3 * P.L;
+    const int v = (blockIdx.x - i * chunks) * 256 + threadIdx.x;  // value 3j + c of the row
+    if (v >= nv) return;
+    const int arrays = P.filter == 0 ? 0 : P.filter == 1 ? 2 : 3;
+    float *out = P.pos + (int64_t)i * nv + v;
+    // the row's three table entries, asked for together: one scalar-load latency instead of three in
+    // a chain.  Both tables hold n entries; an idle slot's are loaded and not looked at.
+    const uint32_t active = P.state[i].active;
+    const int at = index ? index[i] : i;
+    const int from = P.filter != 0 ? src[i] : -1;
+    const int64_t img = active ? at : -1;
+    if (img < 0 || img >= P.n) {
+        *out = __builtin_nanf("");
+        for (int a = 0; a < arrays; ++a) fout[((int64_t)i * arrays + a) * nv + v] = 0u;
+        return;
+    }
+    float x = extract_value(P, img, v);
+    if (P.filter != 0) {
+        uint32_t primed = 0u;
+        float sx = 0.f, sv = 0.f;
+        if (from >= 0 && from < slots) {
+            const uint32_t *si = fin + ((int64_t)(i / slots) * slots + from) * arrays * nv + v;
+            primed = si[0];
+            sx = __uint_as_float(si[nv]);
+            if (arrays == 3) sv = __uint_as_float(si[2 * (int64_t)nv]);
+        }
+        if (!primed) {  // the first value passes through and primes the state (v / dx stay 0)
+            sx = x;
+            sv = 0.f;
+        } else {
+            sx = x = filter_primed(P, x, sx, sv);
+        }
+        uint32_t *so = fout + (int64_t)i * arrays * nv + v;  // primed, then x, then v
+        so[0] = 1u;
+        so[nv] = __float_as_uint(sx);
+        if (arrays == 3) so[2 * (int64_t)nv] = __float_as_uint(sv);
+    }
+    *out = x;
+}
+
 }  // namespace
+
+const char *launch_lm_filter_indexed(const LmFilterIndexedParams &p, hipStream_t s) {
+    const int chunks = (3 * p.base.L + 255) / 256;
+    hipLaunchKernelGGL(lm_filter_indexed_kernel, dim3((unsigned)(p.base.n * chunks)), dim3(256), 0, s, p.base, chunks,
+                       p.slots, p.index, p.src, p.fstate_in, p.base.fstate);
+    return "lm_filter_indexed_kernel";
+}
 
 const char *launch_lm_filter(const LmFilterParams &p, hipStream_t s) {
     const int chunks = (3 * p.L + 255) / 256;

@@ -758,9 +758,9 @@ int zr_track_update_indexed_async(zr_track_state *d_state, size_t n, const zr_tr
                         hip_stream);
 }
 
-int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
-                                    const float *d_positions, const float *d_flag, size_t flag_stride,
-                                    float *d_lm_out, zr_view_desc *d_views, void *hip_stream) {
+static int track_update_positions(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                  const float *d_positions, const float *d_flag, size_t flag_stride,
+                                  const int32_t *d_index, float *d_lm_out, zr_view_desc *d_views, void *hip_stream) {
     return guarded([&]() -> int {
         zr::TrackParams p{};
         if (int rc = track_params(p, d_state, n, cfg, d_views)) return rc;
@@ -772,11 +772,27 @@ int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_
             p.flag = d_flag;
             p.flag_stride = (int)flag_stride;
         }
+        p.index = d_index;
         p.lm_out = d_lm_out;
         zr::launch_track(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
+}
+
+int zr_track_update_positions_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                    const float *d_positions, const float *d_flag, size_t flag_stride,
+                                    float *d_lm_out, zr_view_desc *d_views, void *hip_stream) {
+    return track_update_positions(d_state, n, cfg, d_positions, d_flag, flag_stride, nullptr, d_lm_out, d_views,
+                                  hip_stream);
+}
+
+int zr_track_update_positions_indexed_async(zr_track_state *d_state, size_t n, const zr_track_cfg *cfg,
+                                            const float *d_positions, const float *d_flag, size_t flag_stride,
+                                            const int32_t *d_index, float *d_lm_out, zr_view_desc *d_views,
+                                            void *hip_stream) {
+    return track_update_positions(d_state, n, cfg, d_positions, d_flag, flag_stride, d_index, d_lm_out, d_views,
+                                  hip_stream);
 }
 
 // ---- landmark temporal filters (kernels/lm_filter.hip)
@@ -812,41 +828,77 @@ int zr_lm_filter_state_size(const zr_lm_filter *filter, size_t num_landmarks, si
     });
 }
 
+// the checks both filter entry points share, and the launch parameters they both fill
+static int lm_filter_params(zr::LmFilterParams &p, const zr_lm_filter *filter, const zr_track_cfg *cfg,
+                            const zr_track_state *d_state, size_t n, const float *d_landmarks, size_t lm_stride,
+                            const float *d_flag, size_t flag_stride, float elapsed_s, void *d_filter_state,
+                            float *d_positions) {
+    if (int rc = check_lm_filter(filter)) return rc;
+    if (int rc = check_track_cfg(cfg, n)) return rc;
+    if (int rc = check_extract_inputs(cfg, d_landmarks, lm_stride, d_flag, flag_stride)) return rc;
+    if (!d_positions || (filter->kind != ZR_LM_FILTER_NONE && !d_filter_state))
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "missing positions / filter state");
+    // the time-based filters divide by it: a bad value would poison the state for good
+    if (filter->kind >= ZR_LM_FILTER_ALPHA_BETA && !(std::isfinite(elapsed_s) && elapsed_s > 0.f))
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "a time-based filter needs a finite elapsed time > 0");
+    const uint64_t chunks = (3 * (uint64_t)cfg->num_landmarks + 255) / 256;
+    if (cfg->num_landmarks > (1 << 20) || n * chunks > (uint64_t)INT32_MAX)
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "too many values for one launch");
+    p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+    p.lm = d_landmarks;
+    p.flag = d_flag;
+    p.pos = d_positions;
+    p.fstate = static_cast<uint32_t *>(d_filter_state);
+    p.n = (int)n;
+    p.L = cfg->num_landmarks;
+    p.lm_stride = (int)lm_stride;
+    p.flag_stride = (int)flag_stride;
+    p.kind = cfg->kind;
+    p.in_w = cfg->in_w;
+    p.in_h = cfg->in_h;
+    p.filter = filter->kind;
+    p.p0 = filter->p[0];
+    p.p1 = filter->p[1];
+    p.p2 = filter->p[2];
+    p.elapsed = elapsed_s;
+    return ZR_OK;
+}
+
 int zr_lm_filter_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, const zr_track_state *d_state,
                        size_t n, const float *d_landmarks, size_t lm_stride, const float *d_flag,
                        size_t flag_stride, float elapsed_s, void *d_filter_state, float *d_positions,
                        void *hip_stream) {
     return guarded([&]() -> int {
-        if (int rc = check_lm_filter(filter)) return rc;
-        if (int rc = check_track_cfg(cfg, n)) return rc;
-        if (int rc = check_extract_inputs(cfg, d_landmarks, lm_stride, d_flag, flag_stride)) return rc;
-        if (!d_positions || (filter->kind != ZR_LM_FILTER_NONE && !d_filter_state))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "missing positions / filter state");
-        // the time-based filters divide by it: a bad value would poison the state for good
-        if (filter->kind >= ZR_LM_FILTER_ALPHA_BETA && !(std::isfinite(elapsed_s) && elapsed_s > 0.f))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "a time-based filter needs a finite elapsed time > 0");
-        const uint64_t chunks = (3 * (uint64_t)cfg->num_landmarks + 255) / 256;
-        if (cfg->num_landmarks > (1 << 20) || n * chunks > (uint64_t)INT32_MAX)
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "too many values for one launch");
         zr::LmFilterParams p{};
-        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
-        p.lm = d_landmarks;
-        p.flag = d_flag;
-        p.pos = d_positions;
-        p.fstate = static_cast<uint32_t *>(d_filter_state);
-        p.n = (int)n;
-        p.L = cfg->num_landmarks;
-        p.lm_stride = (int)lm_stride;
-        p.flag_stride = (int)flag_stride;
-        p.kind = cfg->kind;
-        p.in_w = cfg->in_w;
-        p.in_h = cfg->in_h;
-        p.filter = filter->kind;
-        p.p0 = filter->p[0];
-        p.p1 = filter->p[1];
-        p.p2 = filter->p[2];
-        p.elapsed = elapsed_s;
+        if (int rc = lm_filter_params(p, filter, cfg, d_state, n, d_landmarks, lm_stride, d_flag, flag_stride,
+                                      elapsed_s, d_filter_state, d_positions))
+            return rc;
         zr::launch_lm_filter(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_lm_filter_indexed_async(const zr_lm_filter *filter, const zr_track_cfg *cfg, const zr_track_state *d_state,
+                               size_t n, size_t slots, const float *d_landmarks, size_t lm_stride,
+                               const float *d_flag, size_t flag_stride, const int32_t *d_index, const int32_t *d_src,
+                               float elapsed_s, const void *d_filter_state_in, void *d_filter_state_out,
+                               float *d_positions, void *hip_stream) {
+    return guarded([&]() -> int {
+        zr::LmFilterIndexedParams p{};
+        if (int rc = lm_filter_params(p.base, filter, cfg, d_state, n, d_landmarks, lm_stride, d_flag, flag_stride,
+                                      elapsed_s, d_filter_state_out, d_positions))
+            return rc;
+        if (!d_state || !d_src) return set_err(ZR_ERR_INVALID_ARGUMENT, "null state / src");
+        if (slots == 0 || slots > 64 || n % slots != 0)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64 and divide n");
+        if (filter->kind != ZR_LM_FILTER_NONE && (!d_filter_state_in || d_filter_state_in == d_filter_state_out))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the input filter state must be a buffer of its own");
+        p.index = d_index;
+        p.src = d_src;
+        p.fstate_in = static_cast<const uint32_t *>(d_filter_state_in);
+        p.slots = (int)slots;
+        zr::launch_lm_filter_indexed(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });

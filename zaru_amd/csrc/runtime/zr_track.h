@@ -66,6 +66,19 @@ inline size_t lm_filter_words(int filter, size_t L) {
     return filter == 0 ? 0 : (filter == 1 ? 2 : 3) * 3 * L;
 }
 const char *launch_lm_filter(const LmFilterParams &p, hipStream_t s);
+// The indexed, state-gathering form (the multi-object loop: a state follows its object between
+// slots).  Of `base`: n = streams x slots rows, state is required, fstate is the *output* state
+// buffer and every row of it and of pos is written (rows with nothing to filter: zero words, NaN).
+struct LmFilterIndexedParams {
+    LmFilterParams base;
+    const int32_t *index;       // null (row i reads image i), or per row the image of its estimate
+                                // (TrackParams::index); an active row outside [0, n) has no estimate
+    const int32_t *src;         // per row the slot, within its stream, of the incoming state
+                                // (HandManageParams::src); outside [0, slots): the default state
+    const uint32_t *fstate_in;  // the input state buffer, distinct from base.fstate (null for kind 0)
+    int slots;                  // rows per stream
+};
+const char *launch_lm_filter_indexed(const LmFilterIndexedParams &p, hipStream_t s);
 
 // Procrustes analysis of landmark sets (kernels/procrustes.hip; crates/zaru/src/procrustes.rs):
 // one wavefront per set, the arithmetic of kernels/procrustes_math.h.
