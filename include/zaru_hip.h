@@ -488,6 +488,77 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
                                size_t n, const zr_track_cfg *cfg, zr_track_state *d_state, zr_view_desc *d_views,
                                uint64_t *d_reseeded, void *hip_stream);
 
+/* ---- Recognition of the tracked objects inside the multi-object loop -----------------------
+ * Three calls around the embedding network and zr_embed_match_async, issued between the tracker
+ * update (zr_track_update_indexed_async: d_state, d_lm_out) and the next bookkeeping
+ * (zr_multi_manage_async), while landmarks, states and slots still share one arrangement:
+ *     zr_identity_select_async    per object: carry its identity, decide whether it is embedded
+ *                                 this step, build its crop
+ *     zr_identity_compact_async   pack the due objects' crops, with a device count
+ *     (zr_cnn_estimate_device_views_count_async on d_due_views / d_ndue, then
+ *      zr_embed_match_async with d_due_valid as the mask)
+ *     zr_identity_commit_async    write each due object's match and embedding back to it
+ * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
+ * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
+ * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
+ * from the step's current frame at the place the previous frame's landmarks give -- the same one
+ * frame of lag with which the tracker's own RoI is derived. */
+typedef struct {
+    int32_t row;         /* gallery row of the last match, -1: unknown (no row, or past the threshold) */
+    float distance;      /* the nearest row's distance at the last match; +inf: none */
+    uint32_t embeddings; /* embeddings made of this object so far; 0: not identified yet */
+    uint32_t pad;
+    double next_ms;      /* embedded again once now_ms >= next_ms */
+} zr_identity_state;     /* the default state: {-1, +inf, 0, 0, 0.0} and an all-zero embedding */
+#define ZR_IDENTITY_DIM 128
+typedef struct {
+    int slots;              /* K: slots per stream, 1..64 */
+    int num_landmarks;      /* L of d_landmarks */
+    int aspect_w, aspect_h; /* the embedding network's aspect ratio, reduced */
+    float crop_grow;        /* grow_rel factor of the landmarks' bounding rect, >= 0 (0.4) */
+    float threshold;        /* a match is known when distance <= threshold; +inf: the nearest row
+                               always; NaN: never */
+    double interval_ms;     /* re-identification interval, >= 0; 0: every step, +inf: once */
+} zr_identity_cfg;
+/* For row i: when d_state[i].tracked != 0 the incoming identity is row (i / slots) * slots +
+ * d_src[i] of d_in / d_emb_in, d_src being zr_multi_manage_async's d_src of the previous
+ * bookkeeping (as zr_lm_filter_indexed_async reads it); a d_src[i] outside [0, slots) is a new
+ * object and starts from the default state, whatever the slot's previous occupant left behind.  A
+ * row with tracked == 0 gets the default state.  The row is due when it is tracked, embeddings ==
+ * 0 or now_ms >= next_ms, and every x and y of its L landmarks (d_landmarks: n x L x 3, frame px) is
+ * finite.  d_due[i] = 1 or 0.  A due row gets its crop in d_views[i]; other rows of d_views are not
+ * written.  The crop is, in f32 without contraction,
+ *     rect = Rect::bounding(landmark xy)                                      (rect.rs:49-68)
+ *     crop = RotatedRect(rect.grow_rel(crop_grow), 0).grow_to_fit_aspect(aspect)
+ * as a view of frame i / slots, whose size is d_state[i].frame_w x frame_h: bit for bit what
+ * zr_view_describe gives for the host's landmark_crop_view.  State and embedding are written to
+ * row i of d_out / d_emb_out either way.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL pointer, n == 0 or above 2^24,
+ * slots outside 1..64, n not a multiple of slots, num_landmarks < 1, an aspect < 1, crop_grow or
+ * interval_ms negative or NaN, now_ms NaN, d_in == d_out, d_emb_in == d_emb_out, an embedding
+ * buffer not aligned to 8 bytes. */
+int zr_identity_select_async(const zr_identity_cfg *cfg, const zr_track_state *d_state, size_t n,
+                             const float *d_landmarks, const int32_t *d_src, double now_ms,
+                             const zr_identity_state *d_in, const float *d_emb_in, zr_identity_state *d_out,
+                             float *d_emb_out, int32_t *d_due, zr_view_desc *d_views, void *hip_stream);
+/* The due rows packed in row order: for the k-th due row i, d_due_views[k] = d_views[i] and
+ * d_due_of[i] = k; other rows get d_due_of = -1.  *d_ndue = their number, d_due_valid[k] = k <
+ * *d_ndue for every k < n, and *d_total += *d_ndue (d_total may be NULL).  Entries of d_due_views at
+ * and past *d_ndue are not written.  One workgroup scans the flags in 1024-row chunks, so the order
+ * never depends on scheduling.  Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL
+ * pointer other than d_total, n == 0 or above 2^24. */
+int zr_identity_compact_async(const int32_t *d_due, const zr_view_desc *d_views, size_t n,
+                              zr_view_desc *d_due_views, int32_t *d_due_of, int32_t *d_ndue,
+                              int32_t *d_due_valid, uint64_t *d_total, void *hip_stream);
+/* For a row i with k = d_due_of[i] in [0, n): row = d_best_idx[k] when that is >= 0 and
+ * d_best_dist[k] <= threshold, else -1; distance = d_best_dist[k]; embeddings += 1; next_ms = now_ms
+ * + interval_ms; and the row's stored embedding becomes row k of d_dense_emb (the network's output
+ * on d_due_views).  Other rows keep what zr_identity_select_async wrote to d_out / d_emb_out.
+ * Refused as zr_identity_select_async refuses cfg, n and NULL pointers. */
+int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                             const int32_t *d_best_idx, const float *d_best_dist, const float *d_dense_emb,
+                             double now_ms, zr_identity_state *d_out, float *d_emb_out, void *hip_stream);
+
 /* ---- JPEG frame source --------------------------------------------------
  * Replaces decode_jpeg (crates/zaru-image/src/jpeg.rs:107-182) for its libjpeg-turbo backend
  * (turbojpeg 0.5.3: accurate integer IDCT, fancy upsampling, TJPF_RGBA output): the frame is

@@ -76,6 +76,19 @@ class Pose(C.Structure):
                 ("valid", C.c_uint32), ("quat", C.c_float * 4), ("rot", C.c_float * 9)]
 
 
+class IdentityState(C.Structure):
+    """zr_identity_state: what the multi-object loop knows of one object's identity (24 bytes).
+    The default state is {-1, +inf, 0, 0, 0.0}."""
+    _fields_ = [("row", C.c_int32), ("distance", C.c_float), ("embeddings", C.c_uint32), ("pad", C.c_uint32),
+                ("next_ms", C.c_double)]
+
+
+class IdentityCfg(C.Structure):
+    """zr_identity_cfg."""
+    _fields_ = [("slots", C.c_int), ("num_landmarks", C.c_int), ("aspect_w", C.c_int), ("aspect_h", C.c_int),
+                ("crop_grow", C.c_float), ("threshold", C.c_float), ("interval_ms", C.c_double)]
+
+
 def lm_filter_state_size(f: LmFilter, num_landmarks: int) -> int:
     n = C.c_size_t(0)
     check(lib().zr_lm_filter_state_size(C.byref(f), num_landmarks, C.byref(n)))
@@ -123,6 +136,9 @@ SIGNATURES = [
     ("zr_slot_compact_async", _I, [_P, _SZ, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_track_update_indexed_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_embed_match_async", _I, [_P, _SZ, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    ("zr_identity_select_async", _I, [_P, _P, _SZ, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    ("zr_identity_compact_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("zr_identity_commit_async", _I, [_P, _SZ, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),
     ("zr_comm_destroy", None, [_P]),

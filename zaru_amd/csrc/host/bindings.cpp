@@ -512,6 +512,17 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("detection_capacity", &DeviceMultiTracker::detection_capacity)
         .def("detector_frames", &DeviceMultiTracker::detector_frames)
         .def("landmark_images", &DeviceMultiTracker::landmark_images)
+        // recognition of the tracked faces: the embedding network's bytes and a Gallery (kept alive
+        // by the tracker); model b"" or gallery None turns it off
+        .def("set_recognition", [](DeviceMultiTracker &t, const py::bytes &model, const py::object &gallery) {
+            const std::string b = model;
+            t.set_recognition(std::vector<uint8_t>(b.begin(), b.end()),
+                              gallery.is_none() ? nullptr : gallery.cast<const Gallery *>());
+        }, py::arg("model"), py::arg("gallery"), py::keep_alive<1, 3>())
+        .def("set_identify_interval", &DeviceMultiTracker::set_identify_interval, py::arg("ms"))
+        .def("set_identity_threshold", &DeviceMultiTracker::set_identity_threshold, py::arg("distance"))
+        .def("set_identity_crop_grow", &DeviceMultiTracker::set_identity_crop_grow, py::arg("grow"))
+        .def("identity_images", &DeviceMultiTracker::identity_images)
         .def("objects", [](DeviceMultiTracker &t, size_t s) {
             py::list out;
             for (auto &o : t.objects(s)) {
@@ -522,6 +533,16 @@ PYBIND11_MODULE(_zaru_host, m) {
                 d["confidence"] = o.confidence;
                 // the zr_pose record as 21 x f32 (poses_array's layout), when a reference is set
                 if (o.pose) d["pose"] = f32_array(reinterpret_cast<const float *>(&*o.pose), {21});
+                // None: recognition off, or the object not embedded yet
+                d["identity"] = py::none();
+                if (o.identity) {
+                    py::dict id;
+                    id["id"] = o.identity->id;
+                    id["distance"] = o.identity->distance;
+                    id["embeddings"] = o.identity->embeddings;
+                    id["embedding"] = f32_array(o.identity->embedding.data(), {(py::ssize_t)EMBEDDING_DIM});
+                    d["identity"] = id;
+                }
                 out.append(d);
             }
             return out;
@@ -862,6 +883,15 @@ PYBIND11_MODULE(_zaru_host, m) {
             if (!e.embed_first_face(d, host_image(img), out)) return py::none();
             return embedding_array(out);
         });
+    // landmarks: [L][C >= 2] floats, x and y first (an objects() entry's "landmarks")
+    m.def("landmark_crop_view", [](py::array_t<float, py::array::c_style> landmarks, uint32_t image_w, uint32_t image_h,
+                                   uint32_t aspect_w, uint32_t aspect_h, float grow) {
+        if (landmarks.ndim() != 2 || landmarks.shape(0) < 1 || landmarks.shape(1) < 2)
+            throw ZaruError(ZR_ERR_SHAPE, "landmarks must be [L >= 1][C >= 2]");
+        return landmark_crop_view(landmarks.data(), (size_t)landmarks.shape(0), image_w, image_h, aspect_w, aspect_h,
+                                  grow, (size_t)landmarks.shape(1));
+    }, py::arg("landmarks"), py::arg("image_w"), py::arg("image_h"), py::arg("aspect_w"), py::arg("aspect_h"),
+          py::arg("grow") = FaceEmbedder::CROP_GROW);
     py::class_<Gallery>(m, "Gallery")
         .def(py::init<int, size_t>(), py::arg("device") = 0, py::arg("dim") = EMBEDDING_DIM)
         .def("__len__", &Gallery::size)

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 
 #include "hand_tracker.h"
 
@@ -53,6 +54,13 @@ DeviceMultiTracker::DeviceMultiTracker(DetectorNetwork detector, LandmarkNetwork
     pcfg_.thresh = Detector::DEFAULT_THRESHOLD;
     pcfg_.iou = NonMaxSuppression::DEFAULT_IOU_THRESH;
     dcap_ = det_net_.anchors().size();
+    device_ = device;
+    icfg_.slots = slots;
+    icfg_.num_landmarks = landmarker.num_landmarks;
+    icfg_.aspect_w = icfg_.aspect_h = 1;  // the embedding network's, once set
+    icfg_.crop_grow = FaceEmbedder::CROP_GROW;
+    icfg_.threshold = std::numeric_limits<float>::infinity();
+    icfg_.interval_ms = 1000.0;
     check(zr_stream_create(&stream_));
     const size_t nv = n_ * (size_t)slots;
     state_.resize(nv);
@@ -135,6 +143,98 @@ void DeviceMultiTracker::set_filter(const std::optional<FilterParams> &f, float 
     if (prev_elapsed_ && !(std::isfinite(*prev_elapsed_) && *prev_elapsed_ > 0.f)) prev_elapsed_.reset();
 }
 
+void DeviceMultiTracker::set_identify_interval(double ms) {
+    if (!(ms >= 0.0)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "identification interval must be >= 0");
+    icfg_.interval_ms = ms;
+}
+
+void DeviceMultiTracker::set_identity_crop_grow(float g) {
+    if (!(g >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "identity crop grow factor must be >= 0");
+    icfg_.crop_grow = g;
+}
+
+void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, const Gallery *gallery) {
+    if (model.empty() || !gallery) {
+        synchronize();  // the last step's launches still read the network and the gallery
+        embedder_.reset();
+        gallery_ = nullptr;
+        id_ran_ = false;
+        return;
+    }
+    if (gallery->dim() != EMBEDDING_DIM) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery must hold 128-float rows");
+    auto emb = std::make_unique<FaceEmbedder>(model, device_);  // throws before anything changes
+    synchronize();
+    embedder_ = std::move(emb);
+    gallery_ = gallery;
+    const AspectRatio a = embedder_->cnn().aspect();
+    icfg_.aspect_w = (int)a.w;
+    icfg_.aspect_h = (int)a.h;
+    const size_t nv = n_ * (size_t)cfg_.slots;
+    for (int b = 0; b < 2; b++) {
+        id_state_[b].resize(nv);
+        id_emb_[b].resize(nv * EMBEDDING_DIM);
+    }
+    id_dense_emb_.resize(nv * EMBEDDING_DIM);
+    id_best_dist_.resize(nv);
+    id_best_idx_.resize(nv);
+    id_due_.resize(nv);
+    id_due_of_.resize(nv);
+    id_valid_.resize(nv);
+    id_views_.resize(nv);
+    id_due_views_.resize(nv);
+    id_ndue_.resize(1);
+    if (!id_total_.ptr) {
+        id_total_.resize(1);
+        check(zr_memset_async(id_total_.ptr, 0, 8, stream_));
+    }
+    // every object starts over: the default state in both buffers
+    zr_identity_state def{};
+    def.row = -1;
+    def.distance = std::numeric_limits<float>::infinity();
+    const std::vector<zr_identity_state> ds(nv, def);
+    for (int b = 0; b < 2; b++) {
+        check(zr_memcpy_async(id_state_[b].ptr, ds.data(), nv * sizeof(zr_identity_state), 0, stream_));
+        check(zr_memset_async(id_emb_[b].ptr, 0, nv * EMBEDDING_DIM * sizeof(float), stream_));
+    }
+    check(zr_memset_async(id_ndue_.ptr, 0, 4, stream_));
+    check(zr_stream_synchronize(stream_));  // `ds` is pageable and goes out of scope
+    id_flipped_ = false;
+    id_ran_ = false;
+    if (fw_) reset_identity_views();
+}
+
+// a valid view in every entry of the packed crop table, as frame_size() does for the other two
+void DeviceMultiTracker::reset_identity_views() {
+    const size_t K = (size_t)cfg_.slots, nv = n_ * K;
+    std::vector<zr_view_desc> dense(nv, det_tmpl_);
+    for (size_t i = 0; i < nv; i++) dense[i].frame = (uint32_t)(i / K);
+    check(zr_memcpy_async(id_due_views_.ptr, dense.data(), nv * sizeof(zr_view_desc), 0, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+// steps a.-e. of the header; the gallery's rows and size as they are now (Gallery::add may have
+// reallocated them)
+void DeviceMultiTracker::identify(const std::vector<zr_frame> &zf, double now_ms) {
+    const size_t nv = n_ * (size_t)cfg_.slots;
+    const int in = id_flipped_ ? 1 : 0, out = 1 - in;
+    check(zr_identity_select_async(&icfg_, state_.ptr, nv, lm_out_.ptr, src_.ptr, now_ms, id_state_[in].ptr,
+                                   id_emb_[in].ptr, id_state_[out].ptr, id_emb_[out].ptr, id_due_.ptr, id_views_.ptr,
+                                   stream_));
+    check(zr_identity_compact_async(id_due_.ptr, id_views_.ptr, nv, id_due_views_.ptr, id_due_of_.ptr, id_ndue_.ptr,
+                                    id_valid_.ptr, id_total_.ptr, stream_));
+    const Cnn &ec = embedder_->cnn();
+    const ColorMapper cm = ec.color_mapper();
+    float *eouts[1] = {id_dense_emb_.ptr};
+    check(zr_cnn_estimate_device_views_count_async(ec.nn().handle(), zf.data(), n_, id_due_views_.ptr, nv,
+                                                   id_ndue_.ptr, cm.lo, cm.hi, eouts, stream_));
+    check(zr_embed_match_async(id_dense_emb_.ptr, nv, gallery_->device_rows(), gallery_->size(), EMBEDDING_DIM,
+                               id_valid_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, nullptr, stream_));
+    check(zr_identity_commit_async(&icfg_, nv, id_due_of_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, id_dense_emb_.ptr,
+                                   now_ms, id_state_[out].ptr, id_emb_[out].ptr, stream_));
+    id_flipped_ = !id_flipped_;
+    id_ran_ = true;
+}
+
 void DeviceMultiTracker::inject_detections(size_t s, const std::vector<Detection> &dets) {
     if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
     for (const Detection &d : dets) injected_[s].push_back(d);
@@ -169,6 +269,7 @@ void DeviceMultiTracker::frame_size(uint32_t W, uint32_t H) {
     check(zr_memcpy_async(due_views_.ptr, due.data(), n_ * sizeof(zr_view_desc), 0, stream_));
     check(zr_memcpy_async(dense_views_.ptr, dense.data(), nv * sizeof(zr_view_desc), 0, stream_));
     check(zr_stream_synchronize(stream_));
+    if (embedder_) reset_identity_views();
 }
 
 // injected detections go ahead of the detector's result that this step consumes (test hook; the
@@ -215,6 +316,7 @@ void DeviceMultiTracker::apply_injected() {
 
 void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
+    if (embedder_ && std::isnan(now_ms)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "recognition needs a frame clock");
     // both checked before anything is enqueued: this frame's elapsed, and the previous frame's that
     // this step filters with
     float el = 0.f;
@@ -256,6 +358,8 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
         }
         // 2. the head pose of the slots tracked just now, while pose, landmarks and state share a slot
         if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, nv, (size_t)lm_net_.num_landmarks, stream_);
+        // and, at the same place for the same reason, who they are
+        if (embedder_) identify(zf, now_ms);
     }
     // 3. bookkeeping (tracking.rs:129-218)
     check(zr_multi_manage_async(state_.ptr, ids_.ptr, roi_.ptr, src_.ptr, nobj_.ptr, next_id_.ptr, next_det_.ptr,
@@ -319,6 +423,7 @@ std::vector<int32_t> DeviceMultiTracker::dropped_detections() {
 
 uint64_t DeviceMultiTracker::detector_frames() { return read_u64(due_total_); }
 uint64_t DeviceMultiTracker::landmark_images() { return read_u64(lm_total_) + uncompacted_; }
+uint64_t DeviceMultiTracker::identity_images() { return id_total_.ptr ? read_u64(id_total_) : 0; }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {
     if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
@@ -339,6 +444,15 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
         pose.resize(K);  // written per slot before the bookkeeping moved the objects: paired through src
         check(zr_memcpy_async(pose.data(), pose_.out.ptr + s * K, sizeof(zr_pose) * K, 1, stream_));
     }
+    std::vector<zr_identity_state> ist;
+    std::vector<float> iemb;
+    if (embedder_ && id_ran_) {  // written per slot before the bookkeeping, like the pose
+        const int cur = id_flipped_ ? 1 : 0;
+        ist.resize(K);
+        iemb.resize((size_t)K * EMBEDDING_DIM);
+        check(zr_memcpy_async(ist.data(), id_state_[cur].ptr + s * K, sizeof(zr_identity_state) * K, 1, stream_));
+        check(zr_memcpy_async(iemb.data(), id_emb_[cur].ptr + s * K * EMBEDDING_DIM, iemb.size() * 4, 1, stream_));
+    }
     synchronize();
     std::vector<ObjectData> out;
     for (int j = 0; j < no && j < K; j++) {
@@ -350,6 +464,12 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
                                   roi[5 * j + 4]);
         d.confidence = st[j].confidence;
         if (!pose.empty()) d.pose = pose[src[j]];
+        if (!ist.empty() && ist[src[j]].embeddings > 0) {
+            const zr_identity_state &is = ist[src[j]];
+            const float *e = iemb.data() + (size_t)src[j] * EMBEDDING_DIM;
+            d.identity = Identity{gallery_->id_of(is.row), is.distance, is.embeddings,
+                                  std::vector<float>(e, e + EMBEDDING_DIM)};
+        }
         out.push_back(std::move(d));
     }
     return out;

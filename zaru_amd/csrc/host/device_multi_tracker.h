@@ -9,7 +9,8 @@
 //      slot its object held before the previous step's bookkeeping moved it -- and the update on
 //      the filtered positions (zr_track_update_positions_indexed_async),
 //   2. with a pose reference set, the head pose of the slots that update tracked
-//      (zr_procrustes_analyze_tracked_async) -- before step 3 moves the states,
+//      (zr_procrustes_analyze_tracked_async) -- before step 3 moves the states; and with
+//      recognition set (set_recognition) the identity of the tracked objects, see below,
 //   3. the bookkeeping: lost objects leave, the previous step's detections are filtered against
 //      the objects' ROIs, new objects start, the swap_remove de-duplication, the redetection
 //      schedule (zr_multi_manage_async: zr_hand_manage_async's kernel),
@@ -21,6 +22,22 @@
 // Face detectors start an object on the detection's bounding rect, unrotated and with the
 // LandmarkTracker's default padding (examples/facemesh.rs:49-54); the palm detector with
 // HandTracker's grow factor, angle and padding, which makes ("palm", "hand") DeviceHandTracker.
+//
+// Recognition (opt-in, set_recognition): every object carries an identity -- the gallery row it
+// matched, the distance, how often it was embedded, its last embedding and when it is due again --
+// that follows it between slots through step 3's `src`, as the filter state does.  Between steps 2
+// and 3 a step enqueues
+//   a. zr_identity_select_async: each object's identity gathered from the slot it held, the
+//      schedule (never embedded, or now_ms reached its next time), and for a due object the crop
+//      around its landmarks (landmark_crop_view, recognition.h),
+//   b. zr_identity_compact_async: the due crops packed, with a device count,
+//   c. the embedding network on exactly those (zr_cnn_estimate_device_views_count_async),
+//   d. zr_embed_match_async against the gallery's rows as they are at this step,
+//   e. zr_identity_commit_async: match, distance, count, next time and embedding written back.
+// The crop is taken from this step's frame at the place the previous frame's landmarks give: the
+// one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
+// frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
+// landmarks.  A new object is identified at the first step it has a result.
 #pragma once
 #include <memory>
 #include <optional>
@@ -29,6 +46,7 @@
 #include "detection.h"
 #include "device_tracker.h"
 #include "landmark.h"
+#include "recognition.h"
 
 namespace zh {
 
@@ -62,6 +80,23 @@ class DeviceMultiTracker {
     // one Estimator per object, hand/tracking.rs:63,160), its state following it from slot to slot.
     // Replaces the filter and resets every object's state.
     void set_filter(const std::optional<FilterParams> &f, float dt = Estimator::DEFAULT_FILTER_DT);
+    // Recognition of the tracked faces: `model` is the embedding network (FaceEmbedder's, 128
+    // floats per face), `gallery` the rows to match against; it must outlive the tracker or the
+    // next call, and is read at each step (device_rows() and size()), so rows added between steps
+    // (after synchronize(): a step's launches read the rows) count from the next due embedding on.  Rows are only ever appended, so a stored match stays
+    // valid while the gallery grows; after Gallery::clear() call set_recognition again.  An empty
+    // model or a null gallery turns recognition off: a step then enqueues what it did without.
+    // Every call resets every object's identity: each live object is embedded at the next step.
+    void set_recognition(const std::vector<uint8_t> &model, const Gallery *gallery);
+    bool recognition() const { return embedder_ != nullptr; }
+    // an object is embedded again once `ms` passed since its last embedding (default 1000; 0:
+    // every step; +inf: once per object).  Applies from each object's next embedding on.
+    void set_identify_interval(double ms);
+    // a match counts as known when distance <= d (default +inf: the nearest row always, as
+    // Gallery::match; NaN: never).  Applies to the embeddings made from now on.
+    void set_identity_threshold(float d) { icfg_.threshold = d; }
+    // grow_rel factor of the landmarks' bounding rect (default FaceEmbedder::CROP_GROW)
+    void set_identity_crop_grow(float g);
     // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now().
     // With a filter set: `elapsed` seconds between the previous frame and this one (default: the
     // filter's dt), one value for all objects, independent of now_ms.  It belongs to this frame's
@@ -72,12 +107,19 @@ class DeviceMultiTracker {
     int slots() const { return cfg_.slots; }
     const LandmarkNetwork &landmarker() const { return lm_net_; }
 
+    struct Identity {
+        uint64_t id;                   // the caller's id of the matched gallery row; NO_MATCH: unknown
+        float distance;                // to the nearest row at the last embedding (+inf: empty gallery)
+        uint32_t embeddings;           // embeddings made of this object so far (>= 1)
+        std::vector<float> embedding;  // the last one, 128 floats: what a caller enrols an unknown face with
+    };
     struct ObjectData {
         uint64_t id;
         std::vector<float> landmarks;  // L x 3, frame px (the previous step's estimate)
         RotatedRect view_rect;         // the object's ROI (HandData::view_rect)
         float confidence;              // that estimate's Confidence::confidence
         std::optional<zr_pose> pose;   // with a pose reference set
+        std::optional<Identity> identity;  // with recognition set, once the object was embedded
     };
     // after synchronize(): stream s's objects that have a result, in slot order
     std::vector<ObjectData> objects(size_t s);
@@ -88,10 +130,13 @@ class DeviceMultiTracker {
     size_t detection_capacity() const { return dcap_; }
     uint64_t detector_frames();   // frames the detector ran on, summed over the steps
     uint64_t landmark_images();   // views the landmark network ran on, summed over the steps
+    uint64_t identity_images();   // embeddings made, summed over the steps (0 before set_recognition)
 
   private:
     void frame_size(uint32_t W, uint32_t H);
     void apply_injected();
+    void identify(const std::vector<zr_frame> &zf, double now_ms);
+    void reset_identity_views();
     std::vector<int32_t> read_i32(const DeviceArray<int32_t> &a);
     uint64_t read_u64(const DeviceArray<uint64_t> &a);
     std::shared_ptr<const Cnn> det_, lm_;
@@ -122,6 +167,19 @@ class DeviceMultiTracker {
     DeviceFilter filter_;                 // two state buffers of streams x slots rows
     std::optional<float> prev_elapsed_;   // the previous step's `elapsed`: its estimates' (nullopt: dt)
     std::vector<std::vector<Detection>> injected_;
+    // recognition: two state / embedding buffers of streams x slots rows that swap after each step
+    // (id_flipped_: [1] holds the current state), and the packed batch of the due objects
+    int device_ = 0;
+    std::unique_ptr<FaceEmbedder> embedder_;
+    const Gallery *gallery_ = nullptr;
+    zr_identity_cfg icfg_{};
+    bool id_flipped_ = false;
+    bool id_ran_ = false;  // a step has written the identity buffers since set_recognition
+    DeviceArray<zr_identity_state> id_state_[2];
+    DeviceArray<float> id_emb_[2], id_dense_emb_, id_best_dist_;
+    DeviceArray<int32_t> id_due_, id_due_of_, id_ndue_, id_valid_, id_best_idx_;
+    DeviceArray<zr_view_desc> id_views_, id_due_views_;
+    DeviceArray<uint64_t> id_total_;
 };
 
 }  // namespace zh

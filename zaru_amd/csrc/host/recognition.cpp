@@ -49,6 +49,18 @@ bool FaceEmbedder::embed_first_face(Detector &detector, const Image &img, Embedd
     return true;
 }
 
+ViewData landmark_crop_view(const float *landmarks, size_t L, uint32_t image_w, uint32_t image_h, uint32_t aspect_w,
+                            uint32_t aspect_h, float grow, size_t stride) {
+    if (!landmarks || L == 0 || stride < 2 || aspect_w == 0 || aspect_h == 0)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "landmark_crop_view: no landmarks, stride < 2 or a zero aspect");
+    std::vector<Vec2> pts(L);
+    for (size_t j = 0; j < L; j++) pts[j] = {landmarks[j * stride], landmarks[j * stride + 1]};
+    Rect box;
+    Rect::bounding(pts.data(), L, box);
+    const Rect r = box.grow_rel(grow).grow_to_fit_aspect(AspectRatio{aspect_w, aspect_h});
+    return ViewData::full(image_w, image_h).view(RotatedRect(r, 0.f));
+}
+
 // ------------------------------------------------------------------ Gallery
 Gallery::Gallery(int /*device*/, size_t dim) : dim_(dim) {
     if (dim == 0 || dim > (1u << 20)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "bad embedding dimension");

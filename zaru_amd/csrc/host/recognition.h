@@ -42,6 +42,15 @@ class FaceEmbedder {
     std::shared_ptr<const Cnn> cnn_;
 };
 
+// The crop of a tracked face, from its landmarks instead of a detection: `landmarks` are L points
+// of `stride` floats each (x, y first; frame px), and the crop is
+//     Rect::bounding(xy).grow_rel(grow).grow_to_fit_aspect(aspect_w : aspect_h)
+// as a view of the whole image -- FaceEmbedder::crop_view on the landmarks' bounding rect with a
+// free grow factor.  The host restatement of what DeviceMultiTracker's recognition builds on the
+// device (kernels/identity.hip); needs no device.  Throws for L == 0, stride < 2 or a zero aspect.
+ViewData landmark_crop_view(const float *landmarks, size_t L, uint32_t image_w, uint32_t image_h, uint32_t aspect_w,
+                            uint32_t aspect_h, float grow = FaceEmbedder::CROP_GROW, size_t stride = 3);
+
 class Gallery {
   public:
     explicit Gallery(int device = 0, size_t dim = EMBEDDING_DIM);

@@ -2,8 +2,10 @@
 // host/geometry.cpp restates it (crates/zaru-image/src/rect.rs, zaru-linalg), with glibc's
 // own sinf / cosf / atan2f / expf (glibc_math.h).  Every kernel that includes this is compiled
 // with -ffp-contract=off, so each a * b + c rounds twice, as Rust does.  Shared by track.hip
-// (LandmarkTracker::track_impl) and detpost.hip (Detector::detect_impl post-processing).
+// (LandmarkTracker::track_impl), detpost.hip (Detector::detect_impl post-processing) and
+// identity.hip (the crops of the tracked faces).
 #pragma once
+#include "../runtime/zr_kernels.h"
 #include "glibc_math.h"
 
 namespace zr {
@@ -66,6 +68,31 @@ __device__ __forceinline__ RRect view_of(const RRect &parent, const RRect &child
     const float rad = parent.rad + child.rad;
     const V2 c = transform_out(parent, {child.cx, child.cy});
     return from_top_left(c.x - child.w * 0.5f, c.y - child.h * 0.5f, child.w, child.h, rad);
+}
+
+// make_view (session.cpp) on the zr_view {centre, size, rad} of `net`: one entry of the
+// preprocessing's view table
+__device__ __forceinline__ void view_desc(ViewDesc &vd, const RRect &net, int frame) {
+    vd.half_w = net.w * 0.5f;
+    vd.half_h = net.h * 0.5f;
+    vd.tl_x = net.cx - net.w * 0.5f;
+    vd.tl_y = net.cy - net.h * 0.5f;
+    vd.view_w = net.w;
+    vd.view_h = net.h;
+    vd.cos_r = glibc::cosf(net.rad);
+    vd.sin_r = glibc::sinf(net.rad);
+    vd.frame = (uint32_t)frame;
+    vd.pad_ = 0;
+}
+
+// min / max over a wavefront (exact, so the order does not matter)
+__device__ __forceinline__ float wave_min(float v) {
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
 }
 
 // Rect::iou (rect.rs:193-214): intersection of the (top left, top left + size) boxes as a span,

@@ -38,26 +38,7 @@ __device__ void next_view(TrackState &st, ViewDesc &vd, int frame, int aw, int a
     st.local[0] = ltl.x;
     st.local[1] = ltl.y;
     st.local[2] = local.w;
-    // make_view (session.cpp) on the zr_view {centre, size, rad} of `net`
-    vd.half_w = net.w * 0.5f;
-    vd.half_h = net.h * 0.5f;
-    vd.tl_x = net.cx - net.w * 0.5f;
-    vd.tl_y = net.cy - net.h * 0.5f;
-    vd.view_w = net.w;
-    vd.view_h = net.h;
-    vd.cos_r = glibc::cosf(net.rad);
-    vd.sin_r = glibc::sinf(net.rad);
-    vd.frame = (uint32_t)frame;
-    vd.pad_ = 0;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
+    view_desc(vd, net, frame);
 }
 
 // Landmark rows of a ROI that is not tracked this step (lost now or earlier) hold NaN, so a

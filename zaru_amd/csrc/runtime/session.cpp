@@ -1181,6 +1181,106 @@ int zr_slot_compact_async(const int32_t *d_counts, size_t n_streams, size_t slot
     });
 }
 
+// ---- recognition of the tracked objects (kernels/identity.hip)
+static_assert(sizeof(zr_identity_state) == sizeof(zr::IdentityState) && sizeof(zr_identity_state) == 24,
+              "zr_identity_state layout");
+static_assert(offsetof(zr_identity_state, next_ms) == offsetof(zr::IdentityState, next_ms), "zr_identity_state layout");
+static_assert(ZR_IDENTITY_DIM == zr::IDENTITY_DIM, "embedding dimension");
+
+static int check_identity(const zr_identity_cfg *cfg, size_t n, double now_ms) {
+    if (!cfg) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+    if (cfg->slots < 1 || cfg->slots > 64 || n % (size_t)cfg->slots != 0)
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64 and divide n");
+    if (cfg->num_landmarks < 1 || cfg->aspect_w < 1 || cfg->aspect_h < 1 || !(cfg->crop_grow >= 0.f) ||
+        !(cfg->interval_ms >= 0.0) || now_ms != now_ms)
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "bad identity configuration");
+    return ZR_OK;
+}
+
+int zr_identity_select_async(const zr_identity_cfg *cfg, const zr_track_state *d_state, size_t n,
+                             const float *d_landmarks, const int32_t *d_src, double now_ms,
+                             const zr_identity_state *d_in, const float *d_emb_in, zr_identity_state *d_out,
+                             float *d_emb_out, int32_t *d_due, zr_view_desc *d_views, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_state || !d_landmarks || !d_src || !d_in || !d_emb_in || !d_out || !d_emb_out || !d_due || !d_views)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_identity(cfg, n, now_ms)) return rc;
+        if (d_in == d_out || d_emb_in == d_emb_out)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the input identity state must be a buffer of its own");
+        if ((uintptr_t)d_emb_in % 8 || (uintptr_t)d_emb_out % 8)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "embedding buffers must be aligned to 8 bytes");
+        zr::IdentitySelectParams p{};
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.lm = d_landmarks;
+        p.src = d_src;
+        p.in = reinterpret_cast<const zr::IdentityState *>(d_in);
+        p.emb_in = d_emb_in;
+        p.out = reinterpret_cast<zr::IdentityState *>(d_out);
+        p.emb_out = d_emb_out;
+        p.due = d_due;
+        p.views = reinterpret_cast<zr::ViewDesc *>(d_views);
+        p.n = (int)n;
+        p.K = cfg->slots;
+        p.L = cfg->num_landmarks;
+        p.asp_w = cfg->aspect_w;
+        p.asp_h = cfg->aspect_h;
+        p.grow = cfg->crop_grow;
+        p.now = now_ms;
+        zr::launch_identity_select(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_identity_compact_async(const int32_t *d_due, const zr_view_desc *d_views, size_t n,
+                              zr_view_desc *d_due_views, int32_t *d_due_of, int32_t *d_ndue,
+                              int32_t *d_due_valid, uint64_t *d_total, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due || !d_views || !d_due_views || !d_due_of || !d_ndue || !d_due_valid)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+        zr::IdentityCompactParams p{};
+        p.due = d_due;
+        p.views = reinterpret_cast<const zr::ViewDesc *>(d_views);
+        p.due_views = reinterpret_cast<zr::ViewDesc *>(d_due_views);
+        p.due_of = d_due_of;
+        p.ndue = d_ndue;
+        p.due_valid = d_due_valid;
+        p.total = d_total;
+        p.n = (int)n;
+        zr::launch_identity_compact(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                             const int32_t *d_best_idx, const float *d_best_dist, const float *d_dense_emb,
+                             double now_ms, zr_identity_state *d_out, float *d_emb_out, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_best_idx || !d_best_dist || !d_dense_emb || !d_out || !d_emb_out)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_identity(cfg, n, now_ms)) return rc;
+        if ((uintptr_t)d_dense_emb % 8 || (uintptr_t)d_emb_out % 8)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "embedding buffers must be aligned to 8 bytes");
+        zr::IdentityCommitParams p{};
+        p.due_of = d_due_of;
+        p.best_idx = d_best_idx;
+        p.best_dist = d_best_dist;
+        p.dense_emb = d_dense_emb;
+        p.out = reinterpret_cast<zr::IdentityState *>(d_out);
+        p.emb_out = d_emb_out;
+        p.n = (int)n;
+        p.threshold = cfg->threshold;
+        p.now = now_ms;
+        p.interval = cfg->interval_ms;
+        zr::launch_identity_commit(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 int zr_view_describe(const zr_view *views, size_t n, uint32_t frame, zr_view_desc *out) {
     return guarded([&]() -> int {
         if (!views || !out) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");

@@ -204,6 +204,57 @@ struct ReseedParams {
 };
 const char *launch_reseed(const ReseedParams &p, hipStream_t s);
 
+// Recognition of the tracked objects (kernels/identity.hip): what the multi-object loop knows of
+// an object's identity, one record per slot, following the object between slots like the filter
+// state.  Layout mirrored by zr_identity_state in include/zaru_hip.h.
+enum { IDENTITY_DIM = 128 };  // floats per embedding (MobileFaceNet)
+struct IdentityState {
+    int32_t row;          // gallery row of the last match, -1: unknown
+    float distance;       // the nearest row's distance at the last match (+inf: none)
+    uint32_t embeddings;  // embeddings made of this object so far
+    uint32_t pad_;
+    double next_ms;       // the object is embedded again once now >= next_ms
+};
+struct IdentitySelectParams {
+    const TrackState *state;  // [n] tracked != 0: the row has landmarks this step
+    const float *lm;          // [n][L][3] frame px (TrackParams::lm_out)
+    const int32_t *src;       // [n] HandManageParams::src of the previous bookkeeping
+    const IdentityState *in;  // [n] the states the previous step wrote
+    const float *emb_in;      // [n][IDENTITY_DIM]
+    IdentityState *out;       // [n] out, distinct from in
+    float *emb_out;           // [n][IDENTITY_DIM] out, distinct from emb_in
+    int32_t *due;             // [n] out: 1 the row is embedded this step
+    ViewDesc *views;          // [n] out: the crop of a due row (other rows are not written)
+    int n, K, L;
+    int asp_w, asp_h;         // the embedding network's aspect ratio, reduced
+    float grow;               // grow_rel factor of the landmarks' bounding rect
+    double now;
+};
+const char *launch_identity_select(const IdentitySelectParams &p, hipStream_t s);
+struct IdentityCompactParams {
+    const int32_t *due;       // [n]
+    const ViewDesc *views;    // [n]
+    ViewDesc *due_views;      // [n] out: the first *ndue entries
+    int32_t *due_of;          // [n] out: row -> packed image, -1 when not due
+    int32_t *ndue;            // out
+    int32_t *due_valid;       // [n] out: k < *ndue
+    uint64_t *total;          // in / out, may be null
+    int n;
+};
+const char *launch_identity_compact(const IdentityCompactParams &p, hipStream_t s);
+struct IdentityCommitParams {
+    const int32_t *due_of;    // [n]
+    const int32_t *best_idx;  // [n] by packed image (MatchParams::best_idx)
+    const float *best_dist;   // [n]
+    const float *dense_emb;   // [n][IDENTITY_DIM] by packed image
+    IdentityState *out;       // [n] in / out: select's output
+    float *emb_out;           // [n][IDENTITY_DIM]
+    int n;
+    float threshold;
+    double now, interval;
+};
+const char *launch_identity_commit(const IdentityCommitParams &p, hipStream_t s);
+
 // fn: 0 sinf, 1 cosf, 2 expf, 3 atanf, 4 atan2f(a, b) -- glibc_math.h on the device
 const char *launch_glibc_math(int fn, const float *a, const float *b, float *out, int64_t n, hipStream_t s);
 
