@@ -559,6 +559,73 @@ int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t
                              const int32_t *d_best_idx, const float *d_best_dist, const float *d_dense_emb,
                              double now_ms, zr_identity_state *d_out, float *d_emb_out, void *hip_stream);
 
+/* ---- Iris and eye-contour refinement of the tracked faces inside the multi-object loop -----
+ * The reference has the two halves of the cascade -- FaceMeshV1::left_eye / right_eye
+ * (face/landmark/mediapipe.rs:162-192) and EyeNetwork on a cropped left eye, a right eye by
+ * mirroring the image and the landmarks (face/eye.rs:24-27) -- and leaves the middle to the caller.
+ * Here it runs between the tracker update and the next bookkeeping, where recognition's calls are:
+ *     zr_eye_select_async         per eye: validity, the crop, the view the eye network samples
+ *     zr_identity_compact_async   over the 2n entries: the valid eyes packed, with a device count
+ *     zr_eye_crop_async           each packed eye as a network-input-sized RGBA cell of an atlas,
+ *                                 a right eye mirrored
+ *     (zr_cnn_estimate_device_views_count_async on the atlas as the one frame, a constant table of
+ *      identity cell views, and the count)
+ *     zr_eye_commit_async         extract, un-mirror, map to frame px, iris diameter, per entry
+ * Rows are the tracker's n = streams x slots slots; entry 2i is row i's left eye, 2i + 1 its right
+ * eye.  All arithmetic is f32 without contraction, in the reference's order.  With lm = row i's
+ * landmarks (frame px):
+ *     angle = signed_angle_to(lm[263].xy - lm[33].xy, +X)                  (mediapipe.rs:146-160)
+ *     left  = RotatedRect::bounding(angle, {lm[145], lm[33], lm[133], lm[159]})
+ *     right = RotatedRect::bounding(angle, {lm[374], lm[362], lm[263], lm[386]})
+ *     crop  = rect.grow_rel(crop_grow).grow_to_fit_aspect(aspect)
+ * and the eye network samples what Estimator::estimate samples of ViewData::full(frame).view(crop)
+ * (landmark.rs:320-323).  An eye is valid when its row is tracked this step, the x and y of its four
+ * points and of points 33 and 263 are finite, and the ungrown rect has width > 0 and height > 0.
+ * The crop is taken from the step's current frame at the place the previous frame's landmarks give:
+ * recognition's one frame of lag. */
+typedef struct {
+    int slots;              /* K: slots per stream, 1..64 */
+    int num_landmarks;      /* L of d_landmarks, >= 387 (FaceMesh V1 468, V2 478) */
+    int aspect_w, aspect_h; /* the eye network's aspect ratio, reduced */
+    int in_w, in_h;         /* the eye network's input (64 x 64) */
+    float crop_grow;        /* grow_rel factor of the eye rect, >= 0 (0.65: MediaPipe's iris RoI, 2.3 x
+                               the corner-to-corner box) */
+} zr_eye_cfg;
+#define ZR_EYE_POINTS 76    /* 5 iris points (centre first), then 71 contour points */
+/* d_valid[e] = 1 or 0 by the rule above.  A valid entry gets d_views[e], the view of frame i / slots
+ * (size d_state[i].frame_w x frame_h) the network samples -- bit for bit zr_view_describe of the
+ * host's eye_crop_view -- and d_crop_rect[5 e ..] = the crop's {cx, cy, w, h, rad}.  Invalid entries
+ * of d_views and d_crop_rect are not written.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL pointer, n == 0 or above 2^24, slots
+ * outside 1..64, n not a multiple of slots, num_landmarks < 387, an aspect or input size < 1,
+ * crop_grow negative or NaN. */
+int zr_eye_select_async(const zr_eye_cfg *cfg, const zr_track_state *d_state, size_t n, const float *d_landmarks,
+                        int32_t *d_valid, zr_view_desc *d_views, float *d_crop_rect, void *hip_stream);
+/* d_atlas is one RGBA8 image in_w wide and in_h x n_entries high (tightly packed rows), cell k at rows
+ * [k in_h, (k + 1) in_h).  For every entry e with k = d_due_of[e] in [0, min(*d_count, n_entries)):
+ * pixel (x, y) of cell k is the frame pixel d_due_views[k] samples for network-input pixel (x', y)
+ * of an in_w x in_h input -- the preprocessing's lookup, Color::NONE (0) outside the frame or for a
+ * frame index >= n_frames -- with x' = in_w - 1 - x when e is odd (a right eye) and x otherwise.
+ * Cells at and past *d_count are not written.  d_due_views / d_due_of / d_count are
+ * zr_identity_compact_async's over the 2n entries.
+ * Refused: a NULL pointer, no frames, an empty frame, n_entries == 0 or above 2^25, in_w or in_h
+ * outside 1..4096, an atlas not aligned to 4 bytes. */
+int zr_eye_crop_async(const zr_frame *frames, size_t n_frames, const zr_view_desc *d_due_views,
+                      const int32_t *d_due_of, size_t n_entries, const int32_t *d_count, uint8_t *d_atlas,
+                      uint32_t in_w, uint32_t in_h, void *hip_stream);
+/* For every entry e with k = d_due_of[e] in [0, 2n): the 76 points of packed image k -- the iris
+ * (5 x 3) from d_out1 + k stride1, then the contour (71 x 3) from d_out0 + k stride0 (eye.rs:47-64) --
+ * for an odd e un-mirrored (x = -(x - in_w / 2) + in_w / 2, eye.rs:121-125), mapped out as the
+ * Estimator does for the crop (landmark.rs:336-345; z scaled, not moved), x and y through the crop's
+ * transform_out (d_crop_rect[5 e ..], zr_eye_select_async's), written to d_eye_lm[228 e ..];
+ * d_eye_diam[e] = iris_diameter of those frame-px points (eye.rs:105-114); d_eye_valid[e] = 1.
+ * Every other entry gets valid 0, diameter 0 and 228 zero floats.
+ * Refused as zr_eye_select_async refuses cfg, n and NULL pointers, and for stride0 < 213 or
+ * stride1 < 15. */
+int zr_eye_commit_async(const zr_eye_cfg *cfg, size_t n, const int32_t *d_due_of, const float *d_out0,
+                        const float *d_out1, size_t stride0, size_t stride1, const float *d_crop_rect,
+                        float *d_eye_lm, float *d_eye_diam, int32_t *d_eye_valid, void *hip_stream);
+
 /* ---- JPEG frame source --------------------------------------------------
  * Replaces decode_jpeg (crates/zaru-image/src/jpeg.rs:107-182) for its libjpeg-turbo backend
  * (turbojpeg 0.5.3: accurate integer IDCT, fancy upsampling, TJPF_RGBA output): the frame is

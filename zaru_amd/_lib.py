@@ -89,6 +89,12 @@ class IdentityCfg(C.Structure):
                 ("crop_grow", C.c_float), ("threshold", C.c_float), ("interval_ms", C.c_double)]
 
 
+class EyeCfg(C.Structure):
+    """zr_eye_cfg."""
+    _fields_ = [("slots", C.c_int), ("num_landmarks", C.c_int), ("aspect_w", C.c_int), ("aspect_h", C.c_int),
+                ("in_w", C.c_int), ("in_h", C.c_int), ("crop_grow", C.c_float)]
+
+
 def lm_filter_state_size(f: LmFilter, num_landmarks: int) -> int:
     n = C.c_size_t(0)
     check(lib().zr_lm_filter_state_size(C.byref(f), num_landmarks, C.byref(n)))
@@ -139,6 +145,9 @@ SIGNATURES = [
     ("zr_identity_select_async", _I, [_P, _P, _SZ, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_compact_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_commit_async", _I, [_P, _SZ, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
+    ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
+    ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),
+    ("zr_eye_commit_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),
     ("zr_comm_destroy", None, [_P]),

@@ -15,6 +15,7 @@
 #include "recognition.h"
 #include "device_face_loop.h"
 #include "device_tracker.h"
+#include "eye.h"
 
 namespace py = pybind11;
 using namespace zh;
@@ -523,6 +524,12 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("set_identity_threshold", &DeviceMultiTracker::set_identity_threshold, py::arg("distance"))
         .def("set_identity_crop_grow", &DeviceMultiTracker::set_identity_crop_grow, py::arg("grow"))
         .def("identity_images", &DeviceMultiTracker::identity_images)
+        // iris and eye-contour refinement of every tracked face (FaceMesh V1 / V2)
+        .def("set_eye_refinement", &DeviceMultiTracker::set_eye_refinement, py::arg("on"))
+        .def("eye_refinement", &DeviceMultiTracker::eye_refinement)
+        .def("set_eye_crop_grow", &DeviceMultiTracker::set_eye_crop_grow, py::arg("grow"))
+        .def("eye_images", &DeviceMultiTracker::eye_images)
+        .def("stream", [](const DeviceMultiTracker &t) { return reinterpret_cast<uint64_t>(t.stream()); })
         .def("objects", [](DeviceMultiTracker &t, size_t s) {
             py::list out;
             for (auto &o : t.objects(s)) {
@@ -542,6 +549,24 @@ PYBIND11_MODULE(_zaru_host, m) {
                     id["embeddings"] = o.identity->embeddings;
                     id["embedding"] = f32_array(o.identity->embedding.data(), {(py::ssize_t)EMBEDDING_DIM});
                     d["identity"] = id;
+                }
+                // None: eye refinement off, or no step has run it; an invalid eye is None
+                d["eyes"] = py::none();
+                if (o.eyes) {
+                    py::dict eyes;
+                    for (int side = 0; side < 2; side++) {
+                        const auto &e = side ? o.eyes->right : o.eyes->left;
+                        py::object v = py::none();
+                        if (e) {
+                            py::dict ed;
+                            ed["landmarks"] = f32_array(e->landmarks.data(), {(py::ssize_t)EYE_POINTS, (py::ssize_t)3});
+                            ed["iris_diameter"] = e->iris_diameter;
+                            ed["crop"] = e->crop;
+                            v = ed;
+                        }
+                        eyes[side ? "right" : "left"] = v;
+                    }
+                    d["eyes"] = eyes;
                 }
                 out.append(d);
             }
@@ -892,6 +917,72 @@ PYBIND11_MODULE(_zaru_host, m) {
                                   grow, (size_t)landmarks.shape(1));
     }, py::arg("landmarks"), py::arg("image_w"), py::arg("image_h"), py::arg("aspect_w"), py::arg("aspect_h"),
           py::arg("grow") = FaceEmbedder::CROP_GROW);
+    // ---- iris and eye-contour refinement of a face mesh (face/eye.rs + mediapipe.rs:162-192)
+    auto face_mesh_arg = [](const py::array_t<float, py::array::c_style | py::array::forcecast> &lm) {
+        if (lm.ndim() != 2 || lm.shape(0) < 387 || lm.shape(1) != 3)
+            throw ZaruError(ZR_ERR_SHAPE, "face landmarks must be (L >= 387, 3) float32");
+    };
+    auto refined_eye = [](const std::optional<RefinedEye> &e) -> py::object {
+        if (!e) return py::none();
+        py::dict d;
+        d["landmarks"] = f32_array(e->landmarks.positions().data(), {(py::ssize_t)EYE_POINTS, (py::ssize_t)3});
+        d["iris_diameter"] = e->iris_diameter;
+        d["crop"] = e->crop;
+        return d;
+    };
+    m.attr("EYE_CROP_GROW") = EYE_CROP_GROW;
+    // (left, right) RotatedRects of a face mesh, None for an invalid eye
+    m.def("face_eye_rects", [face_mesh_arg](py::array_t<float, py::array::c_style | py::array::forcecast> lm) {
+        face_mesh_arg(lm);
+        const EyeRects r = face_eye_rects(lm.data(), (size_t)lm.shape(0), 3);
+        return py::make_tuple(r.left ? py::cast(*r.left) : py::object(py::none()),
+                              r.right ? py::cast(*r.right) : py::object(py::none()));
+    }, py::arg("landmarks"));
+    m.def("eye_crop_rect", [](const RotatedRect &r, float grow) { return eye_crop_rect(r, grow); }, py::arg("rect"),
+          py::arg("grow") = EYE_CROP_GROW);
+    m.def("eye_crop_view", [](const RotatedRect &r, uint32_t w, uint32_t h, float grow) {
+        return eye_crop_view(r, w, h, grow);
+    }, py::arg("rect"), py::arg("image_w"), py::arg("image_h"), py::arg("grow") = EYE_CROP_GROW);
+    // raw (76, 3) network-px points of one eye -> {landmarks, iris_diameter, crop} in frame px
+    m.def("eye_map_out", [refined_eye](py::array_t<float, py::array::c_style | py::array::forcecast> raw, bool right,
+                                       const RotatedRect &crop) {
+        if (raw.ndim() != 2 || raw.shape(0) != (py::ssize_t)EYE_POINTS || raw.shape(1) != 3)
+            throw ZaruError(ZR_ERR_SHAPE, "eye landmarks are (76, 3) float32");
+        return refined_eye(eye_map_out(raw.data(), right, crop));
+    }, py::arg("raw"), py::arg("right"), py::arg("crop"));
+    py::class_<EyeLandmarks>(m, "EyeLandmarks")
+        .def(py::init([](py::array_t<float, py::array::c_style | py::array::forcecast> p) {
+                 if (p.ndim() != 2 || p.shape(0) != (py::ssize_t)EYE_POINTS || p.shape(1) != 3)
+                     throw ZaruError(ZR_ERR_SHAPE, "eye landmarks are (76, 3) float32");
+                 return new EyeLandmarks(p.data());
+             }), py::arg("positions"))
+        .def("positions", [](const EyeLandmarks &e) { return f32_array(e.positions().data(), {(py::ssize_t)EYE_POINTS, 3}); })
+        .def("iris_center", [](const EyeLandmarks &e) { return f32_array(e.iris_center().data(), {3}); })
+        .def("iris_contour", [](const EyeLandmarks &e) { return f32_array(e.iris_contour().data(), {4, 3}); })
+        .def("eye_contour", [](const EyeLandmarks &e) { return f32_array(e.eye_contour().data(), {(py::ssize_t)EYE_POINTS - 5, 3}); })
+        .def("iris_diameter", &EyeLandmarks::iris_diameter)
+        .def("flip_horizontal_in_place", &EyeLandmarks::flip_horizontal_in_place, py::arg("width"));
+    py::class_<EyeRefiner>(m, "EyeRefiner")
+        .def(py::init<int>(), py::arg("device") = 0)
+        .def("input_width", &EyeRefiner::input_width)
+        .def("refine", [face_mesh_arg, refined_eye](EyeRefiner &r, py::array_t<uint8_t, py::array::c_style> img,
+                                                   py::array_t<float, py::array::c_style | py::array::forcecast> lm, float grow) {
+            face_mesh_arg(lm);
+            const RefinedEyes e = r.refine(host_image(img), lm.data(), (size_t)lm.shape(0), grow);
+            py::dict d;
+            d["left"] = refined_eye(e.left);
+            d["right"] = refined_eye(e.right);
+            return d;
+        }, py::arg("image"), py::arg("face_landmarks"), py::arg("grow") = EYE_CROP_GROW)
+        // the mirrored (in_w, in_h, 4) RGBA crop the network sees of a right eye
+        .def("mirrored_crop", [](const EyeRefiner &r, py::array_t<uint8_t, py::array::c_style> img, const RotatedRect &eye,
+                                 float grow) {
+            const auto px = r.mirrored_crop(host_image(img), eye, grow);
+            const py::ssize_t w = r.input_width();
+            py::array_t<uint8_t> a({(py::ssize_t)(px.size() / 4 / w), w, (py::ssize_t)4});
+            std::memcpy(a.mutable_data(), px.data(), px.size());
+            return a;
+        }, py::arg("image"), py::arg("rect"), py::arg("grow") = EYE_CROP_GROW);
     py::class_<Gallery>(m, "Gallery")
         .def(py::init<int, size_t>(), py::arg("device") = 0, py::arg("dim") = EMBEDDING_DIM)
         .def("__len__", &Gallery::size)

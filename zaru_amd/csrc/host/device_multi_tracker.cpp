@@ -61,6 +61,11 @@ DeviceMultiTracker::DeviceMultiTracker(DetectorNetwork detector, LandmarkNetwork
     icfg_.crop_grow = FaceEmbedder::CROP_GROW;
     icfg_.threshold = std::numeric_limits<float>::infinity();
     icfg_.interval_ms = 1000.0;
+    ecfg_.slots = slots;
+    ecfg_.num_landmarks = landmarker.num_landmarks;
+    ecfg_.aspect_w = ecfg_.aspect_h = 1;  // the eye network's, once loaded
+    ecfg_.in_w = ecfg_.in_h = (int)EYE_INPUT;
+    ecfg_.crop_grow = EYE_CROP_GROW;
     check(zr_stream_create(&stream_));
     const size_t nv = n_ * (size_t)slots;
     state_.resize(nv);
@@ -235,6 +240,92 @@ void DeviceMultiTracker::identify(const std::vector<zr_frame> &zf, double now_ms
     id_ran_ = true;
 }
 
+void DeviceMultiTracker::set_eye_crop_grow(float g) {
+    if (!(g >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "eye crop grow factor must be >= 0");
+    ecfg_.crop_grow = g;
+}
+
+void DeviceMultiTracker::set_eye_refinement(bool on) {
+    if (!on) {
+        synchronize();
+        eye_on_ = eye_ran_ = false;
+        return;
+    }
+    if (!is_face_mesh(lm_net_.kind))
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "eye refinement needs a face mesh (FaceMesh V1 or V2) as the landmarker");
+    const size_t ne = 2 * n_ * (size_t)cfg_.slots;
+    // one atlas cell and one launch-grid row per entry (the preprocessing's grid, and cell rows
+    // that stay exact in f32)
+    if (ne > 65535) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "eye refinement: streams x slots must be <= 32767");
+    if (eye_on_) return;
+    synchronize();
+    if (!eye_cnn_) {
+        auto cnn = network_cnn(NetworkKind::IrisLandmark, device_);
+        const NeuralNetwork &nn = cnn->nn();
+        if (nn.num_outputs() != 2 || nn.output_per_image(0) != 3 * (int64_t)(EYE_POINTS - 5) || nn.output_per_image(1) != 15)
+            throw ZaruError(ZR_ERR_SHAPE, "the eye network must give 71 x 3 contour and 5 x 3 iris floats per image");
+        const uint32_t iw = cnn->input_width(), ih = cnn->input_height();
+        const AspectRatio a = cnn->aspect();
+        ecfg_.aspect_w = (int)a.w;
+        ecfg_.aspect_h = (int)a.h;
+        ecfg_.in_w = (int)iw;
+        ecfg_.in_h = (int)ih;
+        eye_flag_.resize(ne);
+        eye_due_of_.resize(ne);
+        eye_count_.resize(1);
+        eye_due_valid_.resize(ne);
+        eye_valid_.resize(ne);
+        eye_views_.resize(ne);
+        eye_due_views_.resize(ne);
+        eye_cells_.resize(ne);
+        eye_crop_.resize(ne * 5);
+        eye_out_[0].resize(ne * (size_t)nn.output_per_image(0));
+        eye_out_[1].resize(ne * (size_t)nn.output_per_image(1));
+        eye_lm_.resize(ne * EYE_POINTS * 3);
+        eye_diam_.resize(ne);
+        eye_atlas_.resize(ne * (size_t)iw * ih * 4);
+        eye_total_.resize(1);
+        // cell k of the atlas as a view of it: rotation 0 and the input's size, so it samples the
+        // identity (cell rows k * ih + y + 0.5 are exact in f32 for every k the check above admits)
+        std::vector<zr_view> cv(ne);
+        for (size_t k = 0; k < ne; k++)
+            cv[k] = zr_view{(float)iw * 0.5f, (float)(k * ih) + (float)ih * 0.5f, (float)iw, (float)ih, 0.f};
+        std::vector<zr_view_desc> cd(ne);
+        check(zr_view_describe(cv.data(), ne, 0, cd.data()));
+        check(zr_memcpy_async(eye_cells_.ptr, cd.data(), ne * sizeof(zr_view_desc), 0, stream_));
+        check(zr_memset_async(eye_atlas_.ptr, 0, ne * (size_t)iw * ih * 4, stream_));
+        check(zr_memset_async(eye_crop_.ptr, 0, ne * 5 * sizeof(float), stream_));
+        check(zr_memset_async(eye_count_.ptr, 0, 4, stream_));
+        check(zr_memset_async(eye_total_.ptr, 0, 8, stream_));
+        check(zr_stream_synchronize(stream_));  // `cd` is pageable and goes out of scope
+        eye_cnn_ = std::move(cnn);
+    }
+    eye_on_ = true;
+    eye_ran_ = false;
+}
+
+// steps a.-e. of the header
+void DeviceMultiTracker::refine_eyes(const std::vector<zr_frame> &zf) {
+    const size_t nv = n_ * (size_t)cfg_.slots, ne = 2 * nv;
+    const NeuralNetwork &nn = eye_cnn_->nn();
+    const uint32_t iw = eye_cnn_->input_width(), ih = eye_cnn_->input_height();
+    check(zr_eye_select_async(&ecfg_, state_.ptr, nv, lm_out_.ptr, eye_flag_.ptr, eye_views_.ptr, eye_crop_.ptr,
+                              stream_));
+    check(zr_identity_compact_async(eye_flag_.ptr, eye_views_.ptr, ne, eye_due_views_.ptr, eye_due_of_.ptr,
+                                    eye_count_.ptr, eye_due_valid_.ptr, eye_total_.ptr, stream_));
+    check(zr_eye_crop_async(zf.data(), n_, eye_due_views_.ptr, eye_due_of_.ptr, ne, eye_count_.ptr, eye_atlas_.ptr, iw,
+                            ih, stream_));
+    const zr_frame atlas{eye_atlas_.ptr, iw, (uint32_t)(ih * ne), (uint64_t)iw * 4};
+    const ColorMapper cm = eye_cnn_->color_mapper();
+    float *outs[2] = {eye_out_[0].ptr, eye_out_[1].ptr};
+    check(zr_cnn_estimate_device_views_count_async(nn.handle(), &atlas, 1, eye_cells_.ptr, ne, eye_count_.ptr, cm.lo,
+                                                   cm.hi, outs, stream_));
+    check(zr_eye_commit_async(&ecfg_, nv, eye_due_of_.ptr, eye_out_[0].ptr, eye_out_[1].ptr,
+                              (size_t)nn.output_per_image(0), (size_t)nn.output_per_image(1), eye_crop_.ptr,
+                              eye_lm_.ptr, eye_diam_.ptr, eye_valid_.ptr, stream_));
+    eye_ran_ = true;
+}
+
 void DeviceMultiTracker::inject_detections(size_t s, const std::vector<Detection> &dets) {
     if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
     for (const Detection &d : dets) injected_[s].push_back(d);
@@ -360,6 +451,8 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
         if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, nv, (size_t)lm_net_.num_landmarks, stream_);
         // and, at the same place for the same reason, who they are
         if (embedder_) identify(zf, now_ms);
+        // and the eyes of the faces tracked just now
+        if (eye_on_) refine_eyes(zf);
     }
     // 3. bookkeeping (tracking.rs:129-218)
     check(zr_multi_manage_async(state_.ptr, ids_.ptr, roi_.ptr, src_.ptr, nobj_.ptr, next_id_.ptr, next_det_.ptr,
@@ -424,6 +517,7 @@ std::vector<int32_t> DeviceMultiTracker::dropped_detections() {
 uint64_t DeviceMultiTracker::detector_frames() { return read_u64(due_total_); }
 uint64_t DeviceMultiTracker::landmark_images() { return read_u64(lm_total_) + uncompacted_; }
 uint64_t DeviceMultiTracker::identity_images() { return id_total_.ptr ? read_u64(id_total_) : 0; }
+uint64_t DeviceMultiTracker::eye_images() { return eye_total_.ptr ? read_u64(eye_total_) : 0; }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {
     if (s >= n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "stream index out of range");
@@ -453,6 +547,19 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
         check(zr_memcpy_async(ist.data(), id_state_[cur].ptr + s * K, sizeof(zr_identity_state) * K, 1, stream_));
         check(zr_memcpy_async(iemb.data(), id_emb_[cur].ptr + s * K * EMBEDDING_DIM, iemb.size() * 4, 1, stream_));
     }
+    std::vector<int32_t> evalid;
+    std::vector<float> ediam, ecrop, elm;
+    if (eye_on_ && eye_ran_) {  // written per slot before the bookkeeping, like the pose
+        const size_t E = 2 * (size_t)K, e0 = 2 * s * K;
+        evalid.resize(E);
+        ediam.resize(E);
+        ecrop.resize(E * 5);
+        elm.resize(E * EYE_POINTS * 3);
+        check(zr_memcpy_async(evalid.data(), eye_valid_.ptr + e0, E * 4, 1, stream_));
+        check(zr_memcpy_async(ediam.data(), eye_diam_.ptr + e0, E * 4, 1, stream_));
+        check(zr_memcpy_async(ecrop.data(), eye_crop_.ptr + e0 * 5, E * 20, 1, stream_));
+        check(zr_memcpy_async(elm.data(), eye_lm_.ptr + e0 * EYE_POINTS * 3, elm.size() * 4, 1, stream_));
+    }
     synchronize();
     std::vector<ObjectData> out;
     for (int j = 0; j < no && j < K; j++) {
@@ -469,6 +576,18 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
             const float *e = iemb.data() + (size_t)src[j] * EMBEDDING_DIM;
             d.identity = Identity{gallery_->id_of(is.row), is.distance, is.embeddings,
                                   std::vector<float>(e, e + EMBEDDING_DIM)};
+        }
+        if (!evalid.empty()) {
+            Eyes eyes;
+            for (int side = 0; side < 2; side++) {
+                const size_t e = 2 * (size_t)src[j] + side;
+                if (!evalid[e]) continue;
+                const float *c = ecrop.data() + 5 * e, *p = elm.data() + e * EYE_POINTS * 3;
+                (side ? eyes.right : eyes.left) =
+                    Eye{std::vector<float>(p, p + EYE_POINTS * 3), ediam[e],
+                        RotatedRect(Rect::from_center(c[0], c[1], c[2], c[3]), c[4])};
+            }
+            d.eyes = std::move(eyes);
         }
         out.push_back(std::move(d));
     }

@@ -38,6 +38,23 @@
 // one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
 // frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
 // landmarks.  A new object is identified at the first step it has a result.
+//
+// Eye refinement (opt-in, set_eye_refinement; FaceMesh V1 / V2): the iris and eye-contour points of
+// both eyes of every tracked face (host/eye.h: the reference's left_eye / right_eye rects joined to
+// its EyeNetwork).  After step 2 -- and after recognition's calls -- and before step 3 a step enqueues,
+// for every tracked row, every step,
+//   a. zr_eye_select_async: per eye (entry 2i left, 2i + 1 right) validity, crop and sampling view,
+//   b. zr_identity_compact_async over the 2n entries: the valid eyes packed, with a device count,
+//   c. zr_eye_crop_async: each packed eye as a 64 x 64 RGBA cell of an atlas, a right eye mirrored,
+//   d. the eye network on the atlas's first `count` cells (zr_cnn_estimate_device_views_count_async
+//      with a constant table of identity cell views),
+//   e. zr_eye_commit_async: extract, un-mirror, map to frame px, iris diameter, per entry.
+// The atlas (16 KB written and read per eye) is a decision: a mirror flag in the sampler would touch
+// every stem kernel on the benchmarked path.  The results are per slot, written before step 3 moves
+// the objects, and paired with them through `src` in objects(), as the pose and the identity are.
+// The crop is taken from this step's frame at the place the reported (previous-frame) landmarks
+// give: recognition's one frame of lag.  With a filter set the rects come from the filtered landmarks.
+// The eye landmarks themselves are not filtered.
 #pragma once
 #include <memory>
 #include <optional>
@@ -45,6 +62,7 @@
 
 #include "detection.h"
 #include "device_tracker.h"
+#include "eye.h"
 #include "landmark.h"
 #include "recognition.h"
 
@@ -97,12 +115,20 @@ class DeviceMultiTracker {
     void set_identity_threshold(float d) { icfg_.threshold = d; }
     // grow_rel factor of the landmarks' bounding rect (default FaceEmbedder::CROP_GROW)
     void set_identity_crop_grow(float g);
+    // Eye refinement of every tracked face, every step (default off).  Refused unless the
+    // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
+    // step enqueues what it did without, and objects() reports no eyes.
+    void set_eye_refinement(bool on);
+    bool eye_refinement() const { return eye_on_; }
+    // grow_rel factor of the eye rect (default EYE_CROP_GROW, 0.65)
+    void set_eye_crop_grow(float g);
     // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now().
     // With a filter set: `elapsed` seconds between the previous frame and this one (default: the
     // filter's dt), one value for all objects, independent of now_ms.  It belongs to this frame's
     // estimates, which the next step filters and consumes.
     void step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed = std::nullopt);
     void synchronize();
+    void *stream() const { return stream_; }  // the HIP stream every step is enqueued on (event timing)
     size_t streams() const { return n_; }
     int slots() const { return cfg_.slots; }
     const LandmarkNetwork &landmarker() const { return lm_net_; }
@@ -113,6 +139,14 @@ class DeviceMultiTracker {
         uint32_t embeddings;           // embeddings made of this object so far (>= 1)
         std::vector<float> embedding;  // the last one, 128 floats: what a caller enrols an unknown face with
     };
+    struct Eye {
+        std::vector<float> landmarks;  // 76 x 3, frame px: 5 iris points (centre first), 71 contour points
+        float iris_diameter;           // frame px
+        RotatedRect crop;              // the crop the eye network saw (mirrored for a right eye)
+    };
+    struct Eyes {
+        std::optional<Eye> left, right;  // nullopt: the eye was invalid (host/eye.h)
+    };
     struct ObjectData {
         uint64_t id;
         std::vector<float> landmarks;  // L x 3, frame px (the previous step's estimate)
@@ -120,6 +154,7 @@ class DeviceMultiTracker {
         float confidence;              // that estimate's Confidence::confidence
         std::optional<zr_pose> pose;   // with a pose reference set
         std::optional<Identity> identity;  // with recognition set, once the object was embedded
+        std::optional<Eyes> eyes;      // with eye refinement on, once a step has run it
     };
     // after synchronize(): stream s's objects that have a result, in slot order
     std::vector<ObjectData> objects(size_t s);
@@ -131,12 +166,14 @@ class DeviceMultiTracker {
     uint64_t detector_frames();   // frames the detector ran on, summed over the steps
     uint64_t landmark_images();   // views the landmark network ran on, summed over the steps
     uint64_t identity_images();   // embeddings made, summed over the steps (0 before set_recognition)
+    uint64_t eye_images();        // views the eye network ran on, summed over the steps
 
   private:
     void frame_size(uint32_t W, uint32_t H);
     void apply_injected();
     void identify(const std::vector<zr_frame> &zf, double now_ms);
     void reset_identity_views();
+    void refine_eyes(const std::vector<zr_frame> &zf);
     std::vector<int32_t> read_i32(const DeviceArray<int32_t> &a);
     uint64_t read_u64(const DeviceArray<uint64_t> &a);
     std::shared_ptr<const Cnn> det_, lm_;
@@ -180,6 +217,16 @@ class DeviceMultiTracker {
     DeviceArray<int32_t> id_due_, id_due_of_, id_ndue_, id_valid_, id_best_idx_;
     DeviceArray<zr_view_desc> id_views_, id_due_views_;
     DeviceArray<uint64_t> id_total_;
+    // eye refinement: 2 entries per slot (left, right), the packed batch and the atlas it is cropped into
+    std::shared_ptr<const Cnn> eye_cnn_;
+    zr_eye_cfg ecfg_{};
+    bool eye_on_ = false;
+    bool eye_ran_ = false;  // a step has written the eye buffers since it was switched on
+    DeviceArray<int32_t> eye_flag_, eye_due_of_, eye_count_, eye_due_valid_, eye_valid_;
+    DeviceArray<zr_view_desc> eye_views_, eye_due_views_, eye_cells_;
+    DeviceArray<float> eye_crop_, eye_out_[2], eye_lm_, eye_diam_;
+    DeviceArray<uint8_t> eye_atlas_;
+    DeviceArray<uint64_t> eye_total_;
 };
 
 }  // namespace zh

@@ -19,6 +19,7 @@
 #include "plan.h"
 #include "zr_track.h"
 #include "../kernels/procrustes_math.h"
+#include "../kernels/eye_math.h"
 
 namespace {
 
@@ -1276,6 +1277,113 @@ int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t
         p.now = now_ms;
         p.interval = cfg->interval_ms;
         zr::launch_identity_commit(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+// ---- eye refinement of the tracked faces (kernels/eye.hip)
+static int check_eye(const zr_eye_cfg *cfg, size_t n) {
+    if (!cfg) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+    if (cfg->slots < 1 || cfg->slots > 64 || n % (size_t)cfg->slots != 0)
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64 and divide n");
+    if (cfg->num_landmarks < zr::eye::MIN_FACE_LANDMARKS)
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "the eye rects need the face mesh's points up to 386");
+    if (cfg->aspect_w < 1 || cfg->aspect_h < 1 || cfg->in_w < 1 || cfg->in_h < 1 || !(cfg->crop_grow >= 0.f))
+        return set_err(ZR_ERR_INVALID_ARGUMENT, "bad eye configuration");
+    return ZR_OK;
+}
+
+int zr_eye_select_async(const zr_eye_cfg *cfg, const zr_track_state *d_state, size_t n, const float *d_landmarks,
+                        int32_t *d_valid, zr_view_desc *d_views, float *d_crop_rect, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_state || !d_landmarks || !d_valid || !d_views || !d_crop_rect)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_eye(cfg, n)) return rc;
+        zr::EyeSelectParams p{};
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.lm = d_landmarks;
+        p.valid = d_valid;
+        p.views = reinterpret_cast<zr::ViewDesc *>(d_views);
+        p.crop = d_crop_rect;
+        p.n = (int)n;
+        p.K = cfg->slots;
+        p.L = cfg->num_landmarks;
+        p.asp_w = cfg->aspect_w;
+        p.asp_h = cfg->aspect_h;
+        p.grow = cfg->crop_grow;
+        zr::launch_eye_select(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_eye_crop_async(const zr_frame *frames, size_t n_frames, const zr_view_desc *d_due_views,
+                      const int32_t *d_due_of, size_t n_entries, const int32_t *d_count, uint8_t *d_atlas,
+                      uint32_t in_w, uint32_t in_h, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!frames || !d_due_views || !d_due_of || !d_count || !d_atlas)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n_frames == 0 || n_frames > (size_t)INT32_MAX) return set_err(ZR_ERR_INVALID_ARGUMENT, "bad frame count");
+        if (n_entries == 0 || n_entries > (1u << 25)) return set_err(ZR_ERR_INVALID_ARGUMENT, "entries must be 1..2^25");
+        if (in_w == 0 || in_h == 0 || in_w > 4096 || in_h > 4096)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the network input must be 1..4096 pixels a side");
+        if ((uintptr_t)d_atlas % 4) return set_err(ZR_ERR_INVALID_ARGUMENT, "the atlas must be aligned to 4 bytes");
+        for (size_t i = 0; i < n_frames; i++)
+            if (!frames[i].rgba || frames[i].width == 0 || frames[i].height == 0)
+                return set_err(ZR_ERR_INVALID_ARGUMENT, "empty frame");
+        hipStream_t st = (hipStream_t)hip_stream;
+        zr::EyeCropParams p{};
+        p.nframes = (int)n_frames;
+        p.due_views = reinterpret_cast<const zr::ViewDesc *>(d_due_views);
+        p.due_of = d_due_of;
+        p.count = d_count;
+        p.atlas = reinterpret_cast<uint32_t *>(d_atlas);
+        p.entries = (int)n_entries;
+        p.in_w = (int)in_w;
+        p.in_h = (int)in_h;
+        // the frame table goes with the launch's arguments, zr::EYE_CROP_FRAMES frames at a time
+        for (size_t base = 0; base < n_frames; base += zr::EYE_CROP_FRAMES) {
+            p.base = (int)base;
+            for (size_t j = 0; j < (size_t)zr::EYE_CROP_FRAMES; j++) {
+                const size_t i = base + j;
+                p.frames[j] = i < n_frames ? zr::FrameDesc{frames[i].rgba, frames[i].width, frames[i].height,
+                                                           frames[i].row_stride}
+                                           : zr::FrameDesc{nullptr, 0, 0, 0};
+            }
+            zr::launch_eye_crop(p, st);
+            HIP_TRY(hipGetLastError());
+        }
+        return ZR_OK;
+    });
+}
+
+int zr_eye_commit_async(const zr_eye_cfg *cfg, size_t n, const int32_t *d_due_of, const float *d_out0,
+                        const float *d_out1, size_t stride0, size_t stride1, const float *d_crop_rect,
+                        float *d_eye_lm, float *d_eye_diam, int32_t *d_eye_valid, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_out0 || !d_out1 || !d_crop_rect || !d_eye_lm || !d_eye_diam || !d_eye_valid)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_eye(cfg, n)) return rc;
+        if (stride0 < 3 * (size_t)(zr::eye::POINTS - zr::eye::IRIS_POINTS) || stride1 < 3 * (size_t)zr::eye::IRIS_POINTS ||
+            stride0 > (1u << 20) || stride1 > (1u << 20))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the eye network's outputs hold 71 x 3 and 5 x 3 floats per image");
+        zr::EyeCommitParams p{};
+        p.due_of = d_due_of;
+        p.out0 = d_out0;
+        p.out1 = d_out1;
+        p.stride0 = (int64_t)stride0;
+        p.stride1 = (int64_t)stride1;
+        p.crop = d_crop_rect;
+        p.lm = d_eye_lm;
+        p.diam = d_eye_diam;
+        p.valid = d_eye_valid;
+        p.n = (int)n;
+        p.in_w = cfg->in_w;
+        p.asp_w = cfg->aspect_w;
+        p.asp_h = cfg->aspect_h;
+        zr::launch_eye_commit(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });

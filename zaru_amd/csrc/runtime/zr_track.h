@@ -255,6 +255,45 @@ struct IdentityCommitParams {
 };
 const char *launch_identity_commit(const IdentityCommitParams &p, hipStream_t s);
 
+// Eye refinement of the tracked faces (kernels/eye.hip): entry 2i is row i's left eye, 2i + 1 its
+// right eye.  The packing between select and crop is identity_compact_kernel over the 2n entries.
+struct EyeSelectParams {
+    const TrackState *state;  // [n] tracked != 0: the row has landmarks this step
+    const float *lm;          // [n][L][3] frame px
+    int32_t *valid;           // [2n] out
+    ViewDesc *views;          // [2n] out: the view the eye network samples (invalid entries: not written)
+    float *crop;              // [2n][5] out: the crop {cx, cy, w, h, rad} (invalid entries: not written)
+    int n, K, L;
+    int asp_w, asp_h;         // the eye network's aspect ratio, reduced
+    float grow;
+};
+const char *launch_eye_select(const EyeSelectParams &p, hipStream_t s);
+enum { EYE_CROP_FRAMES = 64 };  // frames a launch carries in its arguments: no table to upload
+struct EyeCropParams {
+    FrameDesc frames[EYE_CROP_FRAMES];  // frames [base, base + EYE_CROP_FRAMES) of the caller's table
+    int base;                 // this launch crops the views of those frames; the launch with base 0
+                              // also those of no frame
+    int nframes;              // the whole table: a view whose frame index is >= nframes samples Color::NONE
+    const ViewDesc *due_views;  // [entries] packed
+    const int32_t *due_of;    // [entries] entry -> packed cell, -1: none
+    const int32_t *count;     // packed cells
+    uint32_t *atlas;          // in_w x (in_h * entries) RGBA8, cell k at rows [k in_h, (k + 1) in_h)
+    int entries, in_w, in_h;
+};
+const char *launch_eye_crop(const EyeCropParams &p, hipStream_t s);
+struct EyeCommitParams {
+    const int32_t *due_of;    // [2n]
+    const float *out0, *out1; // the eye network's outputs by packed cell: contour (71 x 3), iris (5 x 3)
+    int64_t stride0, stride1; // floats per cell
+    const float *crop;        // [2n][5] select's
+    float *lm;                // [2n][76][3] out, frame px
+    float *diam;              // [2n] out
+    int32_t *valid;           // [2n] out
+    int n;                    // rows
+    int in_w, asp_w, asp_h;
+};
+const char *launch_eye_commit(const EyeCommitParams &p, hipStream_t s);
+
 // fn: 0 sinf, 1 cosf, 2 expf, 3 atanf, 4 atan2f(a, b) -- glibc_math.h on the device
 const char *launch_glibc_math(int fn, const float *a, const float *b, float *out, int64_t n, hipStream_t s);
 
