@@ -158,6 +158,15 @@ int zr_detect_post_mapped_async(const float *d_logits, const float *d_boxes, con
 int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery, size_t g, size_t dim,
                          const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist,
                          float *d_dist /* [q][g], may be NULL */, void *hip_stream);
+/* The same with the gallery's size read on the device: d_gallery holds g_cap rows, of which the
+ * first *d_g count (*d_g is clamped to [0, g_cap]).  The grid covers the capacity; a tile of rows at
+ * or past *d_g takes no part, and no row at or past *d_g is read.  d_best_idx / d_best_dist are the
+ * bits zr_embed_match_async gives with g = *d_g.  For a gallery that a kernel of the same stream
+ * appends to (zr_identity_enrol_async).  There is no [q][g] output.  Refused as above, and: NULL
+ * d_gallery or d_g, g_cap == 0. */
+int zr_embed_match_count_async(const float *d_query, size_t q, const float *d_gallery, size_t g_cap,
+                               const int32_t *d_g, size_t dim, const int32_t *d_valid, int32_t *d_best_idx,
+                               float *d_best_dist, void *hip_stream);
 
 /* ---- the one collective of the multi-GPU path ------------------------------
  * A communicator over the node's ranks (one process per GPU) for the all-gather of the detection
@@ -498,6 +507,8 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
  *     (zr_cnn_estimate_device_views_count_async on d_due_views / d_ndue, then
  *      zr_embed_match_async with d_due_valid as the mask)
  *     zr_identity_commit_async    write each due object's match and embedding back to it
+ *     (with automatic enrolment: zr_embed_match_count_async in place of the match, and
+ *      zr_identity_enrol_async here: the unknown objects become gallery rows)
  * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
  * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
  * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
@@ -507,10 +518,12 @@ typedef struct {
     int32_t row;         /* gallery row of the last match, -1: unknown (no row, or past the threshold) */
     float distance;      /* the nearest row's distance at the last match; +inf: none */
     uint32_t embeddings; /* embeddings made of this object so far; 0: not identified yet */
-    uint32_t pad;
+    uint32_t flags;      /* ZR_IDENTITY_*: written by zr_identity_enrol_async only, else 0; follows the object */
     double next_ms;      /* embedded again once now_ms >= next_ms */
 } zr_identity_state;     /* the default state: {-1, +inf, 0, 0, 0.0} and an all-zero embedding */
 #define ZR_IDENTITY_DIM 128
+#define ZR_IDENTITY_EVER_KNOWN 1u /* the object matched a row, or was enrolled, at some embedding */
+#define ZR_IDENTITY_ENROLLED 2u   /* the object's row was appended for it by zr_identity_enrol_async */
 typedef struct {
     int slots;              /* K: slots per stream, 1..64 */
     int num_landmarks;      /* L of d_landmarks */
@@ -558,6 +571,32 @@ int zr_identity_compact_async(const int32_t *d_due, const zr_view_desc *d_views,
 int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
                              const int32_t *d_best_idx, const float *d_best_dist, const float *d_dense_emb,
                              double now_ms, zr_identity_state *d_out, float *d_emb_out, void *hip_stream);
+/* Automatic enrolment, issued after zr_identity_commit_async on the committed d_out / d_emb_out, in
+ * one arrangement with it.  The gallery is d_gallery (capacity x 128 floats, *d_count rows in use,
+ * clamped to [0, capacity]) with one id per row in d_ids; matching against it uses
+ * zr_embed_match_count_async with d_count.  The rows i = 0 .. n-1 are walked in row order (stream-major,
+ * then slot order) by one workgroup, so the outcome never depends on scheduling:
+ *   1. a row that was due (d_due_of[i] >= 0) with row >= 0 gets ZR_IDENTITY_EVER_KNOWN;
+ *   2. a row is a candidate when it was due, row == -1, ZR_IDENTITY_EVER_KNOWN is not set, embeddings
+ *      >= min_embeddings, and all 128 floats of its embedding are finite;
+ *   3. a candidate is compared with every row this call has appended so far (the distance of
+ *      zr_embed_match_async, bit for bit; the nearest row, the lowest among equal distances, a NaN
+ *      never wins).  If that distance <= cfg->threshold: row = that row, distance = that distance,
+ *      ZR_IDENTITY_EVER_KNOWN;
+ *   4. otherwise, if *d_count < capacity: its embedding becomes row *d_count, d_ids[*d_count] =
+ *      (*d_next_id)++, row = *d_count, distance = +0.0, flags |= EVER_KNOWN | ENROLLED, ++*d_count and
+ *      ++*d_enrolled_total;
+ *   5. otherwise the object stays unknown and ++*d_dropped.
+ * An object that was ever known is never enrolled (its later embeddings may drift past the
+ * threshold); a NaN threshold enrols every candidate; +inf with an empty gallery enrols the first
+ * candidate and gives every later one its row.  With no candidate the call costs one scan of the rows.
+ * Refused as zr_identity_commit_async refuses cfg, n and NULL pointers (every pointer here is
+ * required), and: capacity == 0 or above 2^31 - 1, dim != 128, min_embeddings == 0, d_emb_out not
+ * aligned to 8 bytes, d_gallery not aligned to 16. */
+int zr_identity_enrol_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of, zr_identity_state *d_out,
+                            const float *d_emb_out, float *d_gallery, uint64_t *d_ids, int32_t *d_count,
+                            uint64_t *d_next_id, size_t capacity, size_t dim, uint32_t min_embeddings,
+                            uint64_t *d_enrolled_total, uint64_t *d_dropped, void *hip_stream);
 
 /* ---- Iris and eye-contour refinement of the tracked faces inside the multi-object loop -----
  * The reference has the two halves of the cascade -- FaceMeshV1::left_eye / right_eye

@@ -79,7 +79,7 @@ class Pose(C.Structure):
 class IdentityState(C.Structure):
     """zr_identity_state: what the multi-object loop knows of one object's identity (24 bytes).
     The default state is {-1, +inf, 0, 0, 0.0}."""
-    _fields_ = [("row", C.c_int32), ("distance", C.c_float), ("embeddings", C.c_uint32), ("pad", C.c_uint32),
+    _fields_ = [("row", C.c_int32), ("distance", C.c_float), ("embeddings", C.c_uint32), ("flags", C.c_uint32),
                 ("next_ms", C.c_double)]
 
 
@@ -145,6 +145,8 @@ SIGNATURES = [
     ("zr_identity_select_async", _I, [_P, _P, _SZ, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_compact_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_commit_async", _I, [_P, _SZ, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
+    ("zr_identity_enrol_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, _P, _P, _P]),
+    ("zr_embed_match_count_async", _I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),
     ("zr_eye_commit_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),

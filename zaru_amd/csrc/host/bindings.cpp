@@ -524,6 +524,13 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("set_identity_threshold", &DeviceMultiTracker::set_identity_threshold, py::arg("distance"))
         .def("set_identity_crop_grow", &DeviceMultiTracker::set_identity_crop_grow, py::arg("grow"))
         .def("identity_images", &DeviceMultiTracker::identity_images)
+        // automatic enrolment into the reserved gallery set_recognition was given; None turns it off
+        .def("set_enrolment", [](DeviceMultiTracker &t, const py::object &gallery, uint64_t first_id, uint32_t min_embeddings) {
+            t.set_enrolment(gallery.is_none() ? nullptr : gallery.cast<Gallery *>(), first_id, min_embeddings);
+        }, py::arg("gallery"), py::arg("first_id") = 0, py::arg("min_embeddings") = 1, py::keep_alive<1, 2>())
+        .def("enrolment", &DeviceMultiTracker::enrolment)
+        .def("enrolled_total", &DeviceMultiTracker::enrolled_total)
+        .def("enrol_dropped", &DeviceMultiTracker::enrol_dropped)
         // iris and eye-contour refinement of every tracked face (FaceMesh V1 / V2)
         .def("set_eye_refinement", &DeviceMultiTracker::set_eye_refinement, py::arg("on"))
         .def("eye_refinement", &DeviceMultiTracker::eye_refinement)
@@ -548,6 +555,7 @@ PYBIND11_MODULE(_zaru_host, m) {
                     id["distance"] = o.identity->distance;
                     id["embeddings"] = o.identity->embeddings;
                     id["embedding"] = f32_array(o.identity->embedding.data(), {(py::ssize_t)EMBEDDING_DIM});
+                    id["enrolled"] = o.identity->enrolled;
                     d["identity"] = id;
                 }
                 // None: eye refinement off, or no step has run it; an invalid eye is None
@@ -988,6 +996,22 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("__len__", &Gallery::size)
         .def("size", &Gallery::size)
         .def("clear", &Gallery::clear)
+        // a gallery the device can append to (DeviceMultiTracker.set_enrolment)
+        .def("reserve", &Gallery::reserve, py::arg("capacity"))
+        .def("reserved", &Gallery::reserved)
+        .def("capacity", &Gallery::capacity)
+        .def("refresh", &Gallery::refresh)
+        .def("enrolled", &Gallery::enrolled)
+        .def("id_of", &Gallery::id_of, py::arg("row"))
+        // (rows [n][dim] f32, ids [n] u64) read back from HBM: what a fresh gallery's add() takes
+        .def("rows", [](Gallery &g) {
+            std::vector<float> r;
+            std::vector<uint64_t> ids;
+            g.rows(r, ids);
+            py::array_t<uint64_t> a((py::ssize_t)ids.size());
+            if (!ids.empty()) std::memcpy(a.mutable_data(), ids.data(), ids.size() * sizeof(uint64_t));
+            return py::make_tuple(f32_array(r.data(), {(py::ssize_t)ids.size(), (py::ssize_t)g.dim()}), a);
+        })
         .def("add", [](Gallery &g, py::array_t<float, py::array::c_style> rows, const std::vector<uint64_t> &ids) {
             if ((size_t)rows.size() != ids.size() * g.dim()) throw ZaruError(ZR_ERR_SHAPE, "rows must be [len(ids)][dim]");
             g.add(rows.data(), ids.data(), ids.size());

@@ -120,6 +120,7 @@ DeviceMultiTracker::~DeviceMultiTracker() {
         (void)zr_stream_synchronize(stream_);
         (void)zr_stream_destroy(stream_);
     }
+    if (enrol_) enrol_->end_enrol(this);  // (the gallery outlives the tracker: set_recognition)
 }
 
 void DeviceMultiTracker::set_redetect_interval(double ms) {
@@ -161,6 +162,7 @@ void DeviceMultiTracker::set_identity_crop_grow(float g) {
 void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, const Gallery *gallery) {
     if (model.empty() || !gallery) {
         synchronize();  // the last step's launches still read the network and the gallery
+        enrol_ = nullptr;
         embedder_.reset();
         gallery_ = nullptr;
         id_ran_ = false;
@@ -169,6 +171,7 @@ void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, cons
     if (gallery->dim() != EMBEDDING_DIM) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery must hold 128-float rows");
     auto emb = std::make_unique<FaceEmbedder>(model, device_);  // throws before anything changes
     synchronize();
+    enrol_ = nullptr;  // enrolment belongs to the gallery it was set for: set_enrolment again
     embedder_ = std::move(emb);
     gallery_ = gallery;
     const AspectRatio a = embedder_->cnn().aspect();
@@ -208,6 +211,29 @@ void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, cons
     if (fw_) reset_identity_views();
 }
 
+void DeviceMultiTracker::set_enrolment(Gallery *gallery, uint64_t first_id, uint32_t min_embeddings) {
+    if (!gallery) {
+        synchronize();
+        enrol_ = nullptr;
+        return;
+    }
+    if (!embedder_ || gallery != gallery_)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "enrolment needs the gallery set_recognition was given");
+    if (!gallery->reserved()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "enrolment needs a reserved gallery (Gallery::reserve)");
+    if (min_embeddings < 1) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "min_embeddings must be >= 1");
+    synchronize();
+    gallery->begin_enrol(this);  // throws while another tracker's enrolling steps may be in flight
+    gallery->end_enrol(this);
+    gallery->seed_next_id(first_id);
+    if (!enrol_counts_.ptr) {
+        enrol_counts_.resize(2);
+        check(zr_memset_async(enrol_counts_.ptr, 0, 16, stream_));
+        check(zr_stream_synchronize(stream_));
+    }
+    enrol_ = gallery;
+    enrol_min_ = min_embeddings;
+}
+
 // a valid view in every entry of the packed crop table, as frame_size() does for the other two
 void DeviceMultiTracker::reset_identity_views() {
     const size_t K = (size_t)cfg_.slots, nv = n_ * K;
@@ -232,10 +258,22 @@ void DeviceMultiTracker::identify(const std::vector<zr_frame> &zf, double now_ms
     float *eouts[1] = {id_dense_emb_.ptr};
     check(zr_cnn_estimate_device_views_count_async(ec.nn().handle(), zf.data(), n_, id_due_views_.ptr, nv,
                                                    id_ndue_.ptr, cm.lo, cm.hi, eouts, stream_));
-    check(zr_embed_match_async(id_dense_emb_.ptr, nv, gallery_->device_rows(), gallery_->size(), EMBEDDING_DIM,
-                               id_valid_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, nullptr, stream_));
+    if (enrol_) {
+        // the gallery's size is the device's: the previous step may have appended to it
+        check(zr_embed_match_count_async(id_dense_emb_.ptr, nv, enrol_->device_rows_mut(), enrol_->capacity(),
+                                         enrol_->device_count(), EMBEDDING_DIM, id_valid_.ptr, id_best_idx_.ptr,
+                                         id_best_dist_.ptr, stream_));
+    } else {
+        check(zr_embed_match_async(id_dense_emb_.ptr, nv, gallery_->device_rows(), gallery_->size(), EMBEDDING_DIM,
+                                   id_valid_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, nullptr, stream_));
+    }
     check(zr_identity_commit_async(&icfg_, nv, id_due_of_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, id_dense_emb_.ptr,
                                    now_ms, id_state_[out].ptr, id_emb_[out].ptr, stream_));
+    if (enrol_)
+        check(zr_identity_enrol_async(&icfg_, nv, id_due_of_.ptr, id_state_[out].ptr, id_emb_[out].ptr,
+                                      enrol_->device_rows_mut(), enrol_->device_ids(), enrol_->device_count(),
+                                      enrol_->device_next_id(), enrol_->capacity(), EMBEDDING_DIM, enrol_min_,
+                                      enrol_counts_.ptr, enrol_counts_.ptr + 1, stream_));
     id_flipped_ = !id_flipped_;
     id_ran_ = true;
 }
@@ -408,6 +446,7 @@ void DeviceMultiTracker::apply_injected() {
 void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
     if (embedder_ && std::isnan(now_ms)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "recognition needs a frame clock");
+    if (enrol_) enrol_->begin_enrol(this);  // refused while another tracker's enrolling steps may be in flight
     // both checked before anything is enqueued: this frame's elapsed, and the previous frame's that
     // this step filters with
     float el = 0.f;
@@ -488,6 +527,7 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
 
 void DeviceMultiTracker::synchronize() {
     if (stream_) check(zr_stream_synchronize(stream_));
+    if (enrol_) enrol_->end_enrol(this);
 }
 
 std::vector<int32_t> DeviceMultiTracker::read_i32(const DeviceArray<int32_t> &a) {
@@ -517,6 +557,20 @@ std::vector<int32_t> DeviceMultiTracker::dropped_detections() {
 uint64_t DeviceMultiTracker::detector_frames() { return read_u64(due_total_); }
 uint64_t DeviceMultiTracker::landmark_images() { return read_u64(lm_total_) + uncompacted_; }
 uint64_t DeviceMultiTracker::identity_images() { return id_total_.ptr ? read_u64(id_total_) : 0; }
+uint64_t DeviceMultiTracker::enrolled_total() {
+    uint64_t v = 0;
+    if (!enrol_counts_.ptr) return v;
+    check(zr_memcpy_async(&v, enrol_counts_.ptr, 8, 1, stream_));
+    synchronize();
+    return v;
+}
+uint64_t DeviceMultiTracker::enrol_dropped() {
+    uint64_t v = 0;
+    if (!enrol_counts_.ptr) return v;
+    check(zr_memcpy_async(&v, enrol_counts_.ptr + 1, 8, 1, stream_));
+    synchronize();
+    return v;
+}
 uint64_t DeviceMultiTracker::eye_images() { return eye_total_.ptr ? read_u64(eye_total_) : 0; }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {
@@ -561,6 +615,7 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
         check(zr_memcpy_async(elm.data(), eye_lm_.ptr + e0 * EYE_POINTS * 3, elm.size() * 4, 1, stream_));
     }
     synchronize();
+    if (enrol_) enrol_->refresh();  // the ids of the rows the steps appended
     std::vector<ObjectData> out;
     for (int j = 0; j < no && j < K; j++) {
         if (src[j] < 0 || src[j] >= K) continue;  // started this step: no result yet
@@ -575,7 +630,7 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
             const zr_identity_state &is = ist[src[j]];
             const float *e = iemb.data() + (size_t)src[j] * EMBEDDING_DIM;
             d.identity = Identity{gallery_->id_of(is.row), is.distance, is.embeddings,
-                                  std::vector<float>(e, e + EMBEDDING_DIM)};
+                                  std::vector<float>(e, e + EMBEDDING_DIM), (is.flags & ZR_IDENTITY_ENROLLED) != 0};
         }
         if (!evalid.empty()) {
             Eyes eyes;

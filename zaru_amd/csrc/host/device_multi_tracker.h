@@ -33,7 +33,9 @@
 //   b. zr_identity_compact_async: the due crops packed, with a device count,
 //   c. the embedding network on exactly those (zr_cnn_estimate_device_views_count_async),
 //   d. zr_embed_match_async against the gallery's rows as they are at this step,
-//   e. zr_identity_commit_async: match, distance, count, next time and embedding written back.
+//   e. zr_identity_commit_async: match, distance, count, next time and embedding written back,
+//   f. with set_enrolment: d. is zr_embed_match_count_async (the gallery's size read on the device),
+//      and zr_identity_enrol_async appends the unknown objects to the gallery (kernels/enrol.hip).
 // The crop is taken from this step's frame at the place the previous frame's landmarks give: the
 // one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
 // frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
@@ -115,6 +117,24 @@ class DeviceMultiTracker {
     void set_identity_threshold(float d) { icfg_.threshold = d; }
     // grow_rel factor of the landmarks' bounding rect (default FaceEmbedder::CROP_GROW)
     void set_identity_crop_grow(float g);
+    // Automatic enrolment: an object that matches no row (after `min_embeddings` embeddings, never
+    // known before, its embedding finite) is appended to the gallery on the device, in the step that
+    // embedded it, and gets a person id: first_id, first_id + 1, ... in row order (stream-major, then
+    // slot order).  Two unknown objects of one step that are within the identity threshold of each
+    // other become one person (zr_identity_enrol_async in include/zaru_hip.h has the rule).  The
+    // gallery row is the person: it outlives the track, the stream and this tracker.
+    // `gallery` must be the gallery set_recognition was given, and reserved (Gallery::reserve);
+    // nullptr turns enrolment off, as does every call of set_recognition.  `first_id` seeds the
+    // gallery's next person id when it has enrolled nobody yet.  With enrolment on a step enqueues
+    // zr_embed_match_count_async in place of the plain match, and zr_identity_enrol_async after the
+    // commit; off, exactly what it did without.
+    // One enrolling tracker per gallery at a time: another tracker may match against the gallery or
+    // enrol into it once this one has synchronised, and its step() throws where that can be seen
+    // (this tracker has stepped since its last synchronize()).
+    void set_enrolment(Gallery *gallery, uint64_t first_id, uint32_t min_embeddings = 1);
+    bool enrolment() const { return enrol_ != nullptr; }
+    uint64_t enrolled_total();  // rows this tracker's steps appended, summed (0 before set_enrolment)
+    uint64_t enrol_dropped();   // candidates that found the gallery full, summed
     // Eye refinement of every tracked face, every step (default off).  Refused unless the
     // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
     // step enqueues what it did without, and objects() reports no eyes.
@@ -138,6 +158,7 @@ class DeviceMultiTracker {
         float distance;                // to the nearest row at the last embedding (+inf: empty gallery)
         uint32_t embeddings;           // embeddings made of this object so far (>= 1)
         std::vector<float> embedding;  // the last one, 128 floats: what a caller enrols an unknown face with
+        bool enrolled;                 // the object's gallery row was appended for it (set_enrolment)
     };
     struct Eye {
         std::vector<float> landmarks;  // 76 x 3, frame px: 5 iris points (centre first), 71 contour points
@@ -217,6 +238,9 @@ class DeviceMultiTracker {
     DeviceArray<int32_t> id_due_, id_due_of_, id_ndue_, id_valid_, id_best_idx_;
     DeviceArray<zr_view_desc> id_views_, id_due_views_;
     DeviceArray<uint64_t> id_total_;
+    Gallery *enrol_ = nullptr;           // gallery_, when enrolment is on
+    uint32_t enrol_min_ = 1;
+    DeviceArray<uint64_t> enrol_counts_;  // [0] rows appended, [1] candidates dropped
     // eye refinement: 2 entries per slot (left, right), the packed batch and the atlas it is cropped into
     std::shared_ptr<const Cnn> eye_cnn_;
     zr_eye_cfg ecfg_{};

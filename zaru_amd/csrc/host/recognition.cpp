@@ -1,6 +1,7 @@
 // recognition.cpp -- see recognition.h.
 #include "recognition.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -77,6 +78,18 @@ Gallery::~Gallery() {
 void Gallery::add(const float *rows, const uint64_t *ids, size_t n) {
     if (n == 0) return;
     if (!rows || !ids) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "null rows or ids");
+    if (reserved_) {  // behind whatever the device appended; the allocation stays where it is
+        refresh();
+        const size_t have = ids_.size();
+        if (n > cap_ - have) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "add past the gallery's reserved capacity");
+        const int32_t count = (int32_t)(have + n);
+        check(zr_memcpy_async(rows_->ptr + have * dim_, rows, n * dim_ * sizeof(float), 0, stream_));
+        check(zr_memcpy_async(dev_ids_.ptr + have, ids, n * sizeof(uint64_t), 0, stream_));
+        check(zr_memcpy_async(count_.ptr, &count, sizeof count, 0, stream_));
+        check(zr_stream_synchronize(stream_));
+        ids_.insert(ids_.end(), ids, ids + n);
+        return;
+    }
     const size_t have = ids_.size(), need = have + n;
     if (need > cap_) {  // grow by doubling, the old rows copied on the gallery's stream
         size_t cap = cap_ ? cap_ : 64;
@@ -95,6 +108,7 @@ void Gallery::add(const float *rows, const uint64_t *ids, size_t n) {
 void Gallery::match(const float *queries, size_t q, uint64_t *ids, float *distances) {
     if (q == 0) return;
     if (!queries || !ids || !distances) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "null queries or outputs");
+    refresh();
     DeviceArray<float> dq(q * dim_), dd(q);
     DeviceArray<int32_t> di(q);
     std::vector<int32_t> idx(q);
@@ -104,6 +118,81 @@ void Gallery::match(const float *queries, size_t q, uint64_t *ids, float *distan
     check(zr_memcpy_async(distances, dd.ptr, q * sizeof(float), 1, stream_));
     check(zr_stream_synchronize(stream_));
     for (size_t i = 0; i < q; i++) ids[i] = id_of(idx[i]);
+}
+
+void Gallery::reserve(size_t capacity) {
+    if (reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is reserved already");
+    if (capacity == 0 || capacity > 0x7fffffffu || capacity < ids_.size())
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "capacity must be 1..2^31-1 and hold the rows the gallery has");
+    const size_t have = ids_.size();
+    if (capacity != cap_) {  // the one move of the rows
+        auto fixed = std::make_unique<DeviceArray<float>>(capacity * dim_);
+        if (have) check(zr_memcpy_async(fixed->ptr, rows_->ptr, have * dim_ * sizeof(float), 2, stream_));
+        check(zr_stream_synchronize(stream_));  // before the old rows are freed
+        rows_ = std::move(fixed);
+        cap_ = capacity;
+    }
+    count_.resize(1);
+    next_id_.resize(1);
+    dev_ids_.resize(capacity);
+    const int32_t count = (int32_t)have;
+    check(zr_memset_async(dev_ids_.ptr, 0, capacity * sizeof(uint64_t), stream_));
+    if (have) check(zr_memcpy_async(dev_ids_.ptr, ids_.data(), have * sizeof(uint64_t), 0, stream_));
+    check(zr_memcpy_async(count_.ptr, &count, sizeof count, 0, stream_));
+    check(zr_memset_async(next_id_.ptr, 0, sizeof(uint64_t), stream_));
+    check(zr_stream_synchronize(stream_));
+    reserved_ = true;
+    enrolled_ = 0;
+}
+
+void Gallery::clear() {
+    ids_.clear();
+    if (!reserved_) return;
+    check(zr_memset_async(count_.ptr, 0, sizeof(int32_t), stream_));
+    check(zr_memset_async(next_id_.ptr, 0, sizeof(uint64_t), stream_));
+    check(zr_stream_synchronize(stream_));
+    enrolled_ = 0;
+}
+
+void Gallery::refresh() {
+    if (!reserved_) return;
+    int32_t count = 0;
+    check(zr_memcpy_async(&count, count_.ptr, sizeof count, 1, stream_));
+    check(zr_stream_synchronize(stream_));
+    const size_t have = ids_.size(), now = (size_t)std::min<int64_t>(std::max<int64_t>(count, 0), (int64_t)cap_);
+    if (now <= have) return;  // rows are only ever appended
+    ids_.resize(now);
+    check(zr_memcpy_async(ids_.data() + have, dev_ids_.ptr + have, (now - have) * sizeof(uint64_t), 1, stream_));
+    check(zr_stream_synchronize(stream_));
+    enrolled_ += now - have;  // add() keeps the mirror itself: what is new here, the device appended
+}
+
+void Gallery::rows(std::vector<float> &out_rows, std::vector<uint64_t> &out_ids) {
+    refresh();
+    out_ids = ids_;
+    out_rows.assign(ids_.size() * dim_, 0.f);
+    if (ids_.empty()) return;
+    check(zr_memcpy_async(out_rows.data(), rows_->ptr, out_rows.size() * sizeof(float), 1, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+void Gallery::seed_next_id(uint64_t first_id) {
+    if (!reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is not reserved");
+    refresh();
+    if (enrolled_) return;
+    check(zr_memcpy_async(next_id_.ptr, &first_id, sizeof first_id, 0, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+void Gallery::begin_enrol(const void *owner) {
+    if (enroller_ && enroller_ != owner)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT,
+                        "another tracker is enrolling into this gallery: synchronize it before this one steps");
+    enroller_ = owner;
+}
+
+void Gallery::end_enrol(const void *owner) {
+    if (enroller_ == owner) enroller_ = nullptr;
 }
 
 // ------------------------------------------------------------------ FaceRecognizer

@@ -3,7 +3,8 @@
 // the crop as 128 floats (MobileFaceNet), compare embeddings by Euclidean distance.
 //   Embedding       the example's `Embedding` with `difference` (lines 31-42)
 //   FaceEmbedder    the example's `FaceEmbedder` (lines 44-93) over a model given as bytes
-//   Gallery         device-resident embeddings with caller ids, nearest-row matching
+//   Gallery         device-resident embeddings with caller ids, nearest-row matching; reserved, one
+//                   the device appends to (automatic enrolment in DeviceMultiTracker)
 //   FaceRecognizer  the whole chain over frames resident in HBM, no host decision between stages
 // Links only against the C ABI, like the rest of host/.
 #pragma once
@@ -61,11 +62,40 @@ class Gallery {
     size_t dim() const { return dim_; }
     // rows: n * dim floats (host)
     void add(const float *rows, const uint64_t *ids, size_t n);
-    void clear() { ids_.clear(); }
+    void clear();
     // queries: q * dim floats (host); ids[i] = NO_MATCH and distances[i] = +inf without a match
     void match(const float *queries, size_t q, uint64_t *ids, float *distances);
     const float *device_rows() const { return rows_ ? rows_->ptr : nullptr; }
     uint64_t id_of(int32_t row) const { return row < 0 || (size_t)row >= ids_.size() ? NO_MATCH : ids_[row]; }
+
+    // A gallery the device can append to (DeviceMultiTracker::set_enrolment).  reserve() fixes the
+    // allocation at `capacity` rows (at least size(); once), so the row pointer never moves under
+    // enqueued steps, and puts the row count (int32), the ids (uint64 per row) and the next person
+    // id (uint64) on the device.  From then on the device's count is the truth and size() / id_of()
+    // answer from a mirror of it that refresh() brings up to date: call it (or a member that does,
+    // see below) after the enrolling tracker's synchronize().  add() refreshes, appends behind the
+    // rows the device appended and updates the count, and throws ZR_ERR_INVALID_ARGUMENT past the
+    // capacity; the caller calls it between steps, after the tracker's synchronize().  clear()
+    // resets both sides (rows, count, next id).  match() and rows() refresh first.
+    // A gallery that was never reserved behaves as it always did.
+    void reserve(size_t capacity);
+    bool reserved() const { return reserved_; }
+    size_t capacity() const { return cap_; }
+    void refresh();
+    size_t enrolled() const { return enrolled_; }  // rows the device appended, as of the last refresh
+    // every row read back from HBM: n * dim floats and n ids -- what a fresh gallery's add() takes
+    void rows(std::vector<float> &out_rows, std::vector<uint64_t> &out_ids);
+    // what zr_identity_enrol_async and zr_embed_match_count_async take (reserved galleries only)
+    float *device_rows_mut() { return rows_ ? rows_->ptr : nullptr; }
+    int32_t *device_count() { return count_.ptr; }
+    uint64_t *device_ids() { return dev_ids_.ptr; }
+    uint64_t *device_next_id() { return next_id_.ptr; }
+    // the next person id becomes `first_id` if the device has enrolled nobody yet (refreshes)
+    void seed_next_id(uint64_t first_id);
+    // One enrolling tracker at a time: a tracker announces the steps it enqueues (begin) and that it
+    // has synchronised (end).  begin throws while another owner's steps may still be in flight.
+    void begin_enrol(const void *owner);
+    void end_enrol(const void *owner);
 
   private:
     size_t dim_;
@@ -73,6 +103,11 @@ class Gallery {
     std::unique_ptr<DeviceArray<float>> rows_;
     size_t cap_ = 0;  // rows allocated
     std::vector<uint64_t> ids_;
+    bool reserved_ = false;
+    size_t enrolled_ = 0;
+    const void *enroller_ = nullptr;  // the tracker whose enqueued steps may append (nullptr: none in flight)
+    DeviceArray<int32_t> count_;
+    DeviceArray<uint64_t> dev_ids_, next_id_;
 };
 
 struct Recognition {

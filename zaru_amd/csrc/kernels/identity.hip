@@ -24,7 +24,7 @@ __device__ __forceinline__ IdentityState default_identity() {
     d.row = -1;
     d.distance = __builtin_inff();
     d.embeddings = 0;
-    d.pad_ = 0;
+    d.flags = 0;
     d.next_ms = 0.0;
     return d;
 }

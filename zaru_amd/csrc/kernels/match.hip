@@ -19,6 +19,11 @@
 // over the gallery tiles and unpacks it; a query that met no candidate (G = 0, masked out, or NaN
 // everywhere) gets row -1 at +inf.  The keys are scratch in plain hipMalloc memory, kept per
 // stream by the caller (runtime/session.cpp).
+//
+// Counted form (MatchParams::gcount, zr_embed_match_count_async): the gallery's size is read from
+// the device, clamped to [0, G]; G is then the capacity the grid covers.  A tile at or past the
+// count returns before it reads a row or writes a key, and the second pass folds only the tiles
+// below the count, so the result is the plain form's at G = the count, bit for bit.
 #include "../runtime/zr_kernels.h"
 
 namespace zr {
@@ -34,6 +39,8 @@ __global__ __launch_bounds__(256) void embed_match_kernel(const MatchParams P, i
     __shared__ unsigned long long best[MT];
     const int qt = blockIdx.x / gtiles, gt = blockIdx.x - qt * gtiles;
     const int q0 = qt * MT, g0 = gt * MT;
+    const int G = P.gcount ? min(max(*P.gcount, 0), P.G) : P.G;
+    if (g0 >= G) return;  // (counted form only: the plain grid has no such tile)
     const int tq = threadIdx.x & 15, tg = threadIdx.x >> 4;
     if (threadIdx.x < MT) best[threadIdx.x] = MATCH_NONE;
     float s[4][4];
@@ -47,7 +54,7 @@ __global__ __launch_bounds__(256) void embed_match_kernel(const MatchParams P, i
             const int r = i / MKC, k = i - r * MKC;  // lanes along k: 128-B runs of a row
             const bool kin = k0 + k < P.D;
             qs[k][r] = (kin && q0 + r < P.Q) ? P.q[(int64_t)(q0 + r) * P.D + k0 + k] : 0.f;
-            gs[k][r] = (kin && g0 + r < P.G) ? P.g[(int64_t)(g0 + r) * P.D + k0 + k] : 0.f;
+            gs[k][r] = (kin && g0 + r < G) ? P.g[(int64_t)(g0 + r) * P.D + k0 + k] : 0.f;
         }
         __syncthreads();
         const int kn = min(MKC, P.D - k0);
@@ -74,9 +81,9 @@ __global__ __launch_bounds__(256) void embed_match_kernel(const MatchParams P, i
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int g = g0 + 4 * tg + j;
-            if (g >= P.G) continue;
+            if (g >= G) continue;
             const float dist = sqrtf(s[i][j]);  // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt)
-            if (P.dist) P.dist[(int64_t)q * P.G + g] = on ? dist : __builtin_inff();
+            if (P.dist) P.dist[(int64_t)q * G + g] = on ? dist : __builtin_inff();
             if (on && dist == dist) {
                 const unsigned long long kk = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)g;
                 key = kk < key ? kk : key;
@@ -94,6 +101,7 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const MatchParams P, 
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= P.Q) return;
     unsigned long long key = MATCH_NONE;
+    if (P.gcount) gtiles = (min(max(*P.gcount, 0), P.G) + MT - 1) / MT;  // the tiles that took part
     for (int gt = 0; gt < gtiles; ++gt) {
         const unsigned long long k = P.keys[(int64_t)gt * qpad + q];
         key = k < key ? k : key;

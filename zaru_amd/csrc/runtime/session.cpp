@@ -1282,6 +1282,44 @@ int zr_identity_commit_async(const zr_identity_cfg *cfg, size_t n, const int32_t
     });
 }
 
+static_assert(offsetof(zr_identity_state, flags) == offsetof(zr::IdentityState, flags), "zr_identity_state layout");
+static_assert(ZR_IDENTITY_EVER_KNOWN == zr::IDENTITY_EVER_KNOWN && ZR_IDENTITY_ENROLLED == zr::IDENTITY_ENROLLED,
+              "identity flags");
+
+int zr_identity_enrol_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of, zr_identity_state *d_out,
+                            const float *d_emb_out, float *d_gallery, uint64_t *d_ids, int32_t *d_count,
+                            uint64_t *d_next_id, size_t capacity, size_t dim, uint32_t min_embeddings,
+                            uint64_t *d_enrolled_total, uint64_t *d_dropped, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_out || !d_emb_out || !d_gallery || !d_ids || !d_count || !d_next_id || !d_enrolled_total ||
+            !d_dropped)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_identity(cfg, n, 0.0)) return rc;
+        if (capacity < 1 || capacity > 0x7fffffffu) return set_err(ZR_ERR_INVALID_ARGUMENT, "capacity must be 1..2^31-1");
+        if (dim != (size_t)zr::IDENTITY_DIM) return set_err(ZR_ERR_INVALID_ARGUMENT, "enrolment needs 128-float rows");
+        if (min_embeddings < 1) return set_err(ZR_ERR_INVALID_ARGUMENT, "min_embeddings must be >= 1");
+        if ((uintptr_t)d_emb_out % 8 || (uintptr_t)d_gallery % 16)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "embeddings must be aligned to 8 bytes, gallery rows to 16");
+        zr::IdentityEnrolParams p{};
+        p.due_of = d_due_of;
+        p.out = reinterpret_cast<zr::IdentityState *>(d_out);
+        p.emb_out = d_emb_out;
+        p.rows = d_gallery;
+        p.ids = d_ids;
+        p.count = d_count;
+        p.next_id = d_next_id;
+        p.enrolled_total = d_enrolled_total;
+        p.dropped = d_dropped;
+        p.n = (int)n;
+        p.capacity = (int)capacity;
+        p.min_embeddings = min_embeddings;
+        p.threshold = cfg->threshold;
+        zr::launch_identity_enrol(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 // ---- eye refinement of the tracked faces (kernels/eye.hip)
 static int check_eye(const zr_eye_cfg *cfg, size_t n) {
     if (!cfg) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
@@ -1582,9 +1620,10 @@ std::mutex g_match_mu;
 std::map<hipStream_t, MatchScratch> g_match_scratch;
 }  // namespace
 
-int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery, size_t g, size_t dim,
-                         const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist, float *d_dist,
-                         void *hip_stream) {
+// g: the gallery's size, or with d_g (the size on the device) its capacity
+static int embed_match(const float *d_query, size_t q, const float *d_gallery, size_t g, const int32_t *d_g, size_t dim,
+                       const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist, float *d_dist,
+                       void *hip_stream) {
     return guarded([&]() -> int {
         if (!d_query || !d_best_idx || !d_best_dist || (g > 0 && !d_gallery))
             return set_err(ZR_ERR_INVALID_ARGUMENT, "null query, gallery or output pointer");
@@ -1603,6 +1642,7 @@ int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery,
         p.best_idx = d_best_idx;
         p.best_dist = d_best_dist;
         p.dist = d_dist;
+        p.gcount = d_g;
         // Per-tile partial results, reduced by the launch's second pass.  One buffer per stream,
         // grown on demand and kept: plain hipMalloc memory, like every other buffer one kernel
         // writes and the next reads.  (With stream-ordered pool memory -- hipMallocAsync per call --
@@ -1624,6 +1664,20 @@ int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery,
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
+}
+
+int zr_embed_match_async(const float *d_query, size_t q, const float *d_gallery, size_t g, size_t dim,
+                         const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist, float *d_dist,
+                         void *hip_stream) {
+    return embed_match(d_query, q, d_gallery, g, nullptr, dim, d_valid, d_best_idx, d_best_dist, d_dist, hip_stream);
+}
+
+int zr_embed_match_count_async(const float *d_query, size_t q, const float *d_gallery, size_t g_cap, const int32_t *d_g,
+                               size_t dim, const int32_t *d_valid, int32_t *d_best_idx, float *d_best_dist,
+                               void *hip_stream) {
+    if (!d_g || !d_gallery || g_cap == 0)
+        return guarded([&]() -> int { return set_err(ZR_ERR_INVALID_ARGUMENT, "the counted match needs a gallery of capacity >= 1 and its device count"); });
+    return embed_match(d_query, q, d_gallery, g_cap, d_g, dim, d_valid, d_best_idx, d_best_dist, nullptr, hip_stream);
 }
 
 int zr_detection_candidates_async(const float *d_logits, const float *d_boxes, uint32_t n,

@@ -165,6 +165,7 @@ struct MatchParams {
     int32_t *best_idx;           // [Q]
     float *best_dist;            // [Q]
     float *dist;                 // [Q][G] or null
+    const int32_t *gcount;       // null, or the gallery's size on the device: clamped to [0, G], G the capacity
 };
 size_t embed_match_scratch(int Q, int G);
 const char *launch_embed_match(const MatchParams &p, hipStream_t s);

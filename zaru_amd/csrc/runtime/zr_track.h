@@ -212,9 +212,10 @@ struct IdentityState {
     int32_t row;          // gallery row of the last match, -1: unknown
     float distance;       // the nearest row's distance at the last match (+inf: none)
     uint32_t embeddings;  // embeddings made of this object so far
-    uint32_t pad_;
+    uint32_t flags;       // IDENTITY_EVER_KNOWN | IDENTITY_ENROLLED: written by identity_enrol_kernel only
     double next_ms;       // the object is embedded again once now >= next_ms
 };
+enum { IDENTITY_EVER_KNOWN = 1, IDENTITY_ENROLLED = 2 };
 struct IdentitySelectParams {
     const TrackState *state;  // [n] tracked != 0: the row has landmarks this step
     const float *lm;          // [n][L][3] frame px (TrackParams::lm_out)
@@ -254,6 +255,22 @@ struct IdentityCommitParams {
     double now, interval;
 };
 const char *launch_identity_commit(const IdentityCommitParams &p, hipStream_t s);
+// Enrolment of the unknown objects after the commit: one workgroup, rows in order.
+struct IdentityEnrolParams {
+    const int32_t *due_of;    // [n] >= 0: the row was embedded this step
+    IdentityState *out;       // [n] in / out: the committed states
+    const float *emb_out;     // [n][IDENTITY_DIM] the committed embeddings
+    float *rows;              // [capacity][IDENTITY_DIM] the gallery, appended to
+    uint64_t *ids;            // [capacity] the rows' ids
+    int32_t *count;           // in / out: rows in the gallery
+    uint64_t *next_id;        // in / out: the next appended row's id
+    uint64_t *enrolled_total; // in / out: += rows appended
+    uint64_t *dropped;        // in / out: += candidates that found the gallery full
+    int n, capacity;
+    uint32_t min_embeddings;
+    float threshold;
+};
+const char *launch_identity_enrol(const IdentityEnrolParams &p, hipStream_t s);
 
 // Eye refinement of the tracked faces (kernels/eye.hip): entry 2i is row i's left eye, 2i + 1 its
 // right eye.  The packing between select and crop is identity_compact_kernel over the 2n entries.

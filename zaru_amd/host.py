@@ -13,6 +13,9 @@ streams=1, slots=4, device=0)``: K objects per stream with stable ids for any de
 ``facemesh_v2``, ``hand``).  ``step(frames, now_ms)`` enqueues only; after ``synchronize()``,
 ``objects(s)`` lists ``{"id", "landmarks", "view_rect", "confidence"}`` (and ``"pose"`` with
 ``set_pose_reference``) for stream ``s``, ``object_counts()`` every stream's objects.
+``set_recognition(model, gallery)`` adds ``"identity"``; with ``gallery.reserve(capacity)`` and
+``set_enrolment(gallery, first_id, min_embeddings=1)`` unknown faces become gallery rows on the
+device, and ``Gallery.rows()`` reads the enrolled people back.
 """
 from __future__ import annotations
 
