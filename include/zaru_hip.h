@@ -116,7 +116,9 @@ int zr_detection_candidates_async(const float *d_logits, const float *d_boxes, u
  * [n][2] = {candidates (conf >= thresh), candidates whose confidence another candidate shares};
  * ties are ordered by anchor index, which is Rust's sort_unstable order only up to 20
  * candidates (nms.rs:66), so a frame with more than 20 candidates and a tie is not pinned by the
- * reference. */
+ * reference.  A NaN IoU (two zero-area boxes) decides as the reference's comparisons do: Remove
+ * mode drops the candidate (nms.rs:73 retains it only while iou < thresh), Average mode leaves it
+ * ungrouped. */
 typedef struct {
     int face;               /* 1 BlazeFace (angle: eye line vs +X), 0 BlazePalm (wrist -> MCP vs +Y) */
     int anchors, params, keypoints;  /* A, values per anchor (16 / 18), keypoints (6 / 7) */
@@ -415,7 +417,9 @@ int zr_track_seed_detections_async(const int32_t *d_count, const float *d_dets, 
  * then counts at the next call (210-218).  Writes every slot's view (idle slots: an empty view),
  * the hand counts and, per slot, the slot the hand had before the call (d_src, -1: new), so the
  * caller can pair hands with the landmarks the update wrote.  Geometry as the host restatement
- * (f32, no contraction): the same decisions as the host HandTracker given the same inputs. */
+ * (f32, no contraction): the same decisions as the host HandTracker given the same inputs.  A NaN
+ * IoU (two zero-area or two infinite rects) is no overlap, in the filter and in the sweep: both
+ * compare `iou >= iou_thresh` as the reference does.  d_nhands[s] is clamped to 0..H when read. */
 typedef struct {
     int slots;              /* H: hand slots per stream */
     float iou_thresh;       /* tracking.rs:38 (0.3) */

@@ -11,7 +11,9 @@
 //     group summed seed first then in ascending order.  Above 20 candidates Rust sorts with
 //     ipnsort, which is not stable: a frame with more than 20 candidates and an exact confidence
 //     tie (sigmoid saturates to 1.0f above logit ~16.6) has an order the reference does not pin;
-//     `ties` reports each frame's candidate and tied-candidate counts so callers can count them.
+//     `ties` reports each frame's candidate and tied-candidate counts so callers can count them;
+//   * a NaN IoU (two zero-area boxes) decides as the reference's comparisons do: Remove mode drops
+//     the candidate (it is retained only while iou < thresh), Average leaves it ungrouped.
 // Candidates (anchor, conf) and their rects live in LDS; the group sums re-decode a member's
 // keypoints from the raw outputs, which is the same arithmetic as decoding it once.
 #include "../runtime/zr_track.h"
@@ -124,7 +126,9 @@ __global__ __launch_bounds__(64) void det_post_kernel(const DetPostParams P) {
             bool in = false;
             if (i < rem) {
                 id = ord[i];
-                in = iou(sx, sy, sw, sh, cr[4 * id], cr[4 * id + 1], cr[4 * id + 2], cr[4 * id + 3]) >= P.iou;
+                const float v = iou(sx, sy, sw, sh, cr[4 * id], cr[4 * id + 1], cr[4 * id + 2], cr[4 * id + 3]);
+                // Remove retains a candidate only while iou < thresh (nms.rs:73); Average groups on >=
+                in = P.mode == 1 ? !(v < P.iou) : v >= P.iou;
             }
             const uint64_t mg = __ballot(i < rem && in), mk = __ballot(i < rem && !in);
             const uint64_t below = (1ull << lane) - 1ull;

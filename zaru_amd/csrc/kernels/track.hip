@@ -221,6 +221,8 @@ __global__ __launch_bounds__(256) void seed_kernel(const SeedParams P) {
 // One thread per video stream: HandTracker::track's bookkeeping (tracking.rs:115-219) over the
 // stream's hand slots, in the reference's order.  Rect::iou and grow_rel as the host restates
 // them (geom_dev.h), so filter and de-duplication decide exactly as the host HandTracker does.
+// Both compare as the reference does, `iou >= thresh`: a NaN IoU (two zero-area or two infinite
+// rects) neither discards a detection nor sweeps a hand.
 __device__ void move_hand(const HandManageParams &P, int to, int from) {
     P.state[to] = P.state[from];
     P.ids[to] = P.ids[from];
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(64) void hand_manage_kernel(const HandManageParams 
     if (P.init_clock) P.next_det[s] = P.now;
     // 1. retain_mut: hands whose tracking was lost leave; the others' ROI is their updated_roi
     int k = 0;
-    const int n = P.nhands[s];
+    const int n = min(max(P.nhands[s], 0), P.H);  // (clamped as slot_compact_kernel clamps it)
     for (int h = 0; h < n; ++h) {
         const int i = base + h;
         if (!P.state[i].active) continue;
@@ -265,7 +267,7 @@ __global__ __launch_bounds__(64) void hand_manage_kernel(const HandManageParams 
             bool ok = true;
             for (int j = 0; j < k0 && ok; ++j) {
                 const float *r = P.hroi + (base + j) * 5;
-                ok = iou(r[0], r[1], r[2], r[3], g.cx, g.cy, g.w, g.h) < P.iou;
+                if (iou(r[0], r[1], r[2], r[3], g.cx, g.cy, g.w, g.h) >= P.iou) ok = false;  // (NaN: kept)
             }
             if (!ok) continue;
             if (k >= P.H) {  // capacity: reported, never silent
