@@ -473,7 +473,13 @@ int zr_cnn_estimate_device_views_async(zr_session *s, const zr_frame *frames, si
                                        float hi, float *const *d_outputs, void *hip_stream);
 /* The same when only the first *d_count (device int, <= n_views) views are needed: the launches
  * skip the work of images at and past it, whose outputs are then undefined.  The count is read
- * by the kernels, so no host decision sits between the step that writes it and this one. */
+ * by the kernels, so no host decision sits between the step that writes it and this one.  Every
+ * kernel clamps what it reads to 0..n_views: a negative count behaves as 0 (nothing below it, so
+ * no output row is defined) and one above n_views as n_views.  The caller still keeps the count
+ * at or below n_views: kernels compare columns against *d_count * P (P: positions per image) in
+ * 32-bit int, which a huge count overflows.  Which kernels run does not depend on the count.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL pointer (d_count included),
+ * n_frames == 0, n_views == 0. */
 int zr_cnn_estimate_device_views_count_async(zr_session *s, const zr_frame *frames, size_t n_frames,
                                              const zr_view_desc *d_views, size_t n_views, const int32_t *d_count,
                                              float lo, float hi, float *const *d_outputs, void *hip_stream);
