@@ -675,6 +675,85 @@ int zr_eye_commit_async(const zr_eye_cfg *cfg, size_t n, const int32_t *d_due_of
                         const float *d_out1, size_t stride0, size_t stride1, const float *d_crop_rect,
                         float *d_eye_lm, float *d_eye_diam, int32_t *d_eye_valid, void *hip_stream);
 
+/* ---- Every stream's tracked objects as one packed batch -------------------------------------
+ * What a caller of the multi-object loop reads after a step -- per stream, the objects that have a
+ * result -- gathered on the device into dense records behind a device count, so the read-out is
+ * one bounded copy however many streams there are (kernels/export.hip).
+ * With no = clamp(d_nobjects[s], 0, slots), slot j < no of stream s is exported iff r =
+ * d_src[s * slots + j] (zr_multi_manage_async's d_src of the last bookkeeping) lies in [0, slots):
+ * an object started by that bookkeeping has no result yet.  The exported objects are numbered in
+ * stream-then-slot order and the k-th goes to record k of every output array.  The bookkeeping has
+ * moved the objects but not their results, so a record is gathered from two slots of its stream:
+ *     slot j   id (d_ids), roi (d_roi, 5 floats), confidence (d_state[..].confidence)
+ *     slot r   landmarks (L x 3 floats), pose, identity state and embedding, both eyes (entries 2 r
+ *              and 2 r + 1 of the eye arrays)
+ * Outputs: *d_count = the exported objects; d_stream_offsets[s] = the exported objects of the
+ * streams before s (n_streams + 1 entries: stream s owns records [off[s], off[s + 1])); and per
+ * record, in arrays of n_streams * slots rows, zr_export_header, the landmarks, and for each
+ * optional group that is given: the zr_pose record as it is; zr_export_identity and the 128-float
+ * embedding when the state's embeddings != 0, else all zero; per eye (entries 2 k, 2 k + 1) valid 1
+ * with diameter, crop and the 76 x 3 landmarks when its valid flag != 0, else all zero.  The
+ * header's flags say which parts are present.  Every value is copied bit for bit.
+ * An optional group -- {d_pose, d_out_pose}, {d_id_state, d_id_emb, d_out_identity, d_out_emb},
+ * {the four eye inputs, the four eye outputs} -- is all NULL when its feature is off; its outputs
+ * are then not touched.  Records at and past *d_count are not written.
+ * One workgroup scans the streams in 1024-stream chunks and writes count, offsets and headers, so
+ * the order never depends on scheduling and nothing is placed with atomics; a second launch copies
+ * the payload, one workgroup per record, lanes on consecutive dwords (16-byte accesses when
+ * 3 L is a multiple of 4 and the arrays are 16-byte aligned).
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL args or required pointer, an
+ * optional group given only in part, n_streams == 0, slots outside 1..64, num_landmarks == 0,
+ * n_streams * slots above 2^31 - 1, num_landmarks above 2^20. */
+#define ZR_EXPORT_POSE 1u      /* the pose record was copied (the pose group is given) */
+#define ZR_EXPORT_IDENTITY 2u  /* the object has been embedded: identity and embedding are its own */
+#define ZR_EXPORT_EYE_LEFT 4u  /* the left eye was valid */
+#define ZR_EXPORT_EYE_RIGHT 8u /* the right eye was valid */
+typedef struct {
+    uint64_t id;       /* the object's id */
+    int32_t stream;    /* s */
+    int32_t slot;      /* j: the slot the object holds now */
+    float roi[5];      /* the object's ROI {cx, cy, w, h, rad} */
+    float confidence;  /* the reported estimate's confidence */
+    uint32_t flags;    /* ZR_EXPORT_* */
+    uint32_t reserved; /* 0 */
+} zr_export_header;    /* 48 bytes */
+typedef struct {
+    int32_t row;         /* zr_identity_state's row, distance, embeddings and flags */
+    float distance;
+    uint32_t embeddings;
+    uint32_t flags;
+} zr_export_identity;
+typedef struct {
+    /* the tracker's arrays; rows are n_streams * slots slots, stream-major */
+    const int32_t *d_nobjects;     /* [n_streams] */
+    const int32_t *d_src;          /* [rows] */
+    const uint64_t *d_ids;         /* [rows] */
+    const float *d_roi;            /* [rows][5] */
+    const zr_track_state *d_state; /* [rows] */
+    const float *d_landmarks;      /* [rows][L][3] */
+    const zr_pose *d_pose;                /* [rows], optional */
+    const zr_identity_state *d_id_state;  /* [rows], optional with d_id_emb */
+    const float *d_id_emb;                /* [rows][128] */
+    const int32_t *d_eye_valid;           /* [2 rows], optional with the next three */
+    const float *d_eye_diam;              /* [2 rows] */
+    const float *d_eye_crop;              /* [2 rows][5] */
+    const float *d_eye_lm;                /* [2 rows][76][3] */
+    /* outputs */
+    int32_t *d_count;
+    int32_t *d_stream_offsets;     /* [n_streams + 1] */
+    zr_export_header *d_header;    /* [rows] */
+    float *d_out_landmarks;        /* [rows][L][3] */
+    zr_pose *d_out_pose;                /* [rows] */
+    zr_export_identity *d_out_identity; /* [rows] */
+    float *d_out_emb;                   /* [rows][128] */
+    int32_t *d_out_eye_valid;           /* [2 rows] */
+    float *d_out_eye_diam;              /* [2 rows] */
+    float *d_out_eye_crop;              /* [2 rows][5] */
+    float *d_out_eye_lm;                /* [2 rows][76][3] */
+} zr_multi_export_args;
+int zr_multi_export_async(const zr_multi_export_args *args, size_t n_streams, size_t slots, size_t num_landmarks,
+                          void *hip_stream);
+
 /* ---- JPEG frame source --------------------------------------------------
  * Replaces decode_jpeg (crates/zaru-image/src/jpeg.rs:107-182) for its libjpeg-turbo backend
  * (turbojpeg 0.5.3: accurate integer IDCT, fancy upsampling, TJPF_RGBA output): the frame is

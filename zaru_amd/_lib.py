@@ -95,6 +95,35 @@ class EyeCfg(C.Structure):
                 ("in_w", C.c_int), ("in_h", C.c_int), ("crop_grow", C.c_float)]
 
 
+class ExportHeader(C.Structure):
+    """zr_export_header: the fixed part of one record of zr_multi_export_async (48 bytes)."""
+    _fields_ = [("id", C.c_uint64), ("stream", C.c_int32), ("slot", C.c_int32), ("roi", C.c_float * 5),
+                ("confidence", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExportIdentity(C.Structure):
+    """zr_export_identity: an exported object's identity (16 bytes); all zero when it has none."""
+    _fields_ = [("row", C.c_int32), ("distance", C.c_float), ("embeddings", C.c_uint32), ("flags", C.c_uint32)]
+
+
+EXPORT_POSE, EXPORT_IDENTITY, EXPORT_EYE_LEFT, EXPORT_EYE_RIGHT = 1, 2, 4, 8
+
+
+class MultiExportArgs(C.Structure):
+    """zr_multi_export_args: the tracker's arrays and the packed outputs, device pointers.  An optional
+    group (pose; identity; eyes) is left None when its feature is off."""
+    INPUTS = ("d_nobjects", "d_src", "d_ids", "d_roi", "d_state", "d_landmarks")
+    POSE = ("d_pose", "d_out_pose")
+    IDENTITY = ("d_id_state", "d_id_emb", "d_out_identity", "d_out_emb")
+    EYES = ("d_eye_valid", "d_eye_diam", "d_eye_crop", "d_eye_lm", "d_out_eye_valid", "d_out_eye_diam",
+            "d_out_eye_crop", "d_out_eye_lm")
+    _fields_ = [(n, C.c_void_p) for n in (
+        "d_nobjects", "d_src", "d_ids", "d_roi", "d_state", "d_landmarks", "d_pose", "d_id_state", "d_id_emb",
+        "d_eye_valid", "d_eye_diam", "d_eye_crop", "d_eye_lm", "d_count", "d_stream_offsets", "d_header",
+        "d_out_landmarks", "d_out_pose", "d_out_identity", "d_out_emb", "d_out_eye_valid", "d_out_eye_diam",
+        "d_out_eye_crop", "d_out_eye_lm")]
+
+
 def lm_filter_state_size(f: LmFilter, num_landmarks: int) -> int:
     n = C.c_size_t(0)
     check(lib().zr_lm_filter_state_size(C.byref(f), num_landmarks, C.byref(n)))
@@ -150,6 +179,7 @@ SIGNATURES = [
     ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),
     ("zr_eye_commit_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    ("zr_multi_export_async", _I, [_P, _SZ, _SZ, _SZ, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),
     ("zr_comm_destroy", None, [_P]),

@@ -537,6 +537,74 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("set_eye_crop_grow", &DeviceMultiTracker::set_eye_crop_grow, py::arg("grow"))
         .def("eye_images", &DeviceMultiTracker::eye_images)
         .def("stream", [](const DeviceMultiTracker &t) { return reinterpret_cast<uint64_t>(t.stream()); })
+        // every stream's objects at once: snapshot() enqueues the device-side pack and returns;
+        // objects_packed() waits for it (taking one now if none is pending) and returns numpy arrays of
+        // `count` rows -- what [objects(s) for s] reports, stream s owning rows
+        // [stream_offsets[s], stream_offsets[s + 1]).  A feature that is off or has not run is left out.
+        .def("snapshot", &DeviceMultiTracker::snapshot)
+        .def("objects_packed", [](DeviceMultiTracker &t) {
+            DeviceMultiTracker::PackedObjects p;
+            {
+                py::gil_scoped_release nogil;
+                p = t.objects_packed();
+            }
+            const py::ssize_t c = (py::ssize_t)p.count, L = (py::ssize_t)p.num_landmarks;
+            py::dict d;
+            d["count"] = p.count;
+            py::array_t<int32_t> off((py::ssize_t)t.streams() + 1), stream(c), slot(c);
+            std::memcpy(off.mutable_data(), p.stream_offsets, (size_t)off.size() * 4);
+            d["stream_offsets"] = off;
+            py::array_t<uint64_t> id(c);
+            py::array_t<uint32_t> flags(c);
+            py::array_t<float> rect({c, (py::ssize_t)5}), conf(c);
+            for (py::ssize_t k = 0; k < c; k++) {
+                const zr_export_header &h = p.headers[k];
+                stream.mutable_data()[k] = h.stream;
+                slot.mutable_data()[k] = h.slot;
+                id.mutable_data()[k] = h.id;
+                flags.mutable_data()[k] = h.flags;
+                std::memcpy(rect.mutable_data() + 5 * k, h.roi, 20);
+                std::memcpy(conf.mutable_data() + k, &h.confidence, 4);
+            }
+            d["stream"] = stream;
+            d["slot"] = slot;
+            d["id"] = id;
+            d["flags"] = flags;
+            d["view_rect"] = rect;  // {cx, cy, w, h, radians} per row
+            d["confidence"] = conf;
+            d["landmarks"] = f32_array(p.landmarks, {c, L, (py::ssize_t)3});
+            // the zr_pose records as 21 x f32 per row (poses_array's layout)
+            if (p.pose) d["pose"] = f32_array(reinterpret_cast<const float *>(p.pose), {c, (py::ssize_t)21});
+            if (p.identity) {
+                py::array_t<uint64_t> pid(c);
+                py::array_t<float> dist(c);
+                py::array_t<uint32_t> nemb(c);
+                py::array_t<bool> enrolled(c), present(c);
+                for (py::ssize_t k = 0; k < c; k++) {
+                    const zr_export_identity &i = p.identity[k];
+                    pid.mutable_data()[k] = p.identity_id[k];
+                    std::memcpy(dist.mutable_data() + k, &i.distance, 4);
+                    nemb.mutable_data()[k] = i.embeddings;
+                    enrolled.mutable_data()[k] = (i.flags & ZR_IDENTITY_ENROLLED) != 0;
+                    present.mutable_data()[k] = (p.headers[k].flags & ZR_EXPORT_IDENTITY) != 0;
+                }
+                d["identity_id"] = pid;
+                d["identity_distance"] = dist;
+                d["identity_embeddings"] = nemb;
+                d["identity_enrolled"] = enrolled;
+                d["identity_present"] = present;
+                d["embedding"] = f32_array(p.embedding, {c, (py::ssize_t)EMBEDDING_DIM});
+            }
+            if (p.eye_valid) {
+                py::array_t<int32_t> valid({c, (py::ssize_t)2});
+                std::memcpy(valid.mutable_data(), p.eye_valid, (size_t)valid.size() * 4);
+                d["eye_valid"] = valid;
+                d["iris_diameter"] = f32_array(p.iris_diameter, {c, (py::ssize_t)2});
+                d["eye_crop"] = f32_array(p.eye_crop, {c, (py::ssize_t)2, (py::ssize_t)5});
+                d["eye_landmarks"] = f32_array(p.eye_landmarks, {c, (py::ssize_t)2, (py::ssize_t)EYE_POINTS, (py::ssize_t)3});
+            }
+            return d;
+        })
         .def("objects", [](DeviceMultiTracker &t, size_t s) {
             py::list out;
             for (auto &o : t.objects(s)) {

@@ -120,6 +120,8 @@ DeviceMultiTracker::~DeviceMultiTracker() {
         (void)zr_stream_synchronize(stream_);
         (void)zr_stream_destroy(stream_);
     }
+    if (snap_.copy_stream) (void)zr_stream_destroy(snap_.copy_stream);  // idle: objects_packed waits for its copies
+    if (snap_.event) (void)zr_event_destroy(snap_.event);
     if (enrol_) enrol_->end_enrol(this);  // (the gallery outlives the tracker: set_recognition)
 }
 
@@ -160,6 +162,7 @@ void DeviceMultiTracker::set_identity_crop_grow(float g) {
 }
 
 void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, const Gallery *gallery) {
+    snap_.pending = false;  // a snapshot's identities name rows of the gallery it was taken with
     if (model.empty() || !gallery) {
         synchronize();  // the last step's launches still read the network and the gallery
         enrol_ = nullptr;
@@ -212,6 +215,7 @@ void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, cons
 }
 
 void DeviceMultiTracker::set_enrolment(Gallery *gallery, uint64_t first_id, uint32_t min_embeddings) {
+    snap_.pending = false;
     if (!gallery) {
         synchronize();
         enrol_ = nullptr;
@@ -645,6 +649,137 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
             d.eyes = std::move(eyes);
         }
         out.push_back(std::move(d));
+    }
+    return out;
+}
+
+// objects(s)'s conditions decide which optional groups the export gets; the buffers are the
+// snapshot's own, so the steps enqueued behind it write elsewhere
+void DeviceMultiTracker::snapshot() {
+    const size_t K = (size_t)cfg_.slots, nv = n_ * K, L = (size_t)lm_net_.num_landmarks;
+    Snapshot &sn = snap_;
+    if (!sn.event) check(zr_event_create(&sn.event));
+    if (!sn.copy_stream) check(zr_stream_create(&sn.copy_stream));
+    sn.pose = pose_.on() && pose_.ran && pose_.out.n >= nv;
+    sn.identity = embedder_ && id_ran_;
+    sn.eyes = eye_on_ && eye_ran_;
+    sn.enrol = sn.identity && enrol_ != nullptr;
+    sn.count.resize(1);
+    sn.offsets.resize(n_ + 1);
+    sn.header.resize(nv);
+    sn.lm.resize(nv * L * 3);
+    sn.h_small.resize(n_ + 3);
+    zr_multi_export_args a{};
+    a.d_nobjects = nobj_.ptr;
+    a.d_src = src_.ptr;
+    a.d_ids = ids_.ptr;
+    a.d_roi = roi_.ptr;
+    a.d_state = state_.ptr;
+    a.d_landmarks = lm_out_.ptr;
+    a.d_count = sn.count.ptr;
+    a.d_stream_offsets = sn.offsets.ptr;
+    a.d_header = sn.header.ptr;
+    a.d_out_landmarks = sn.lm.ptr;
+    if (sn.pose) {
+        sn.pose_out.resize(nv);
+        a.d_pose = pose_.out.ptr;
+        a.d_out_pose = sn.pose_out.ptr;
+    }
+    if (sn.identity) {
+        const int cur = id_flipped_ ? 1 : 0;
+        sn.ident.resize(nv);
+        sn.emb.resize(nv * EMBEDDING_DIM);
+        a.d_id_state = id_state_[cur].ptr;
+        a.d_id_emb = id_emb_[cur].ptr;
+        a.d_out_identity = sn.ident.ptr;
+        a.d_out_emb = sn.emb.ptr;
+    }
+    if (sn.eyes) {
+        sn.eye_valid.resize(2 * nv);
+        sn.eye_diam.resize(2 * nv);
+        sn.eye_crop.resize(2 * nv * 5);
+        sn.eye_lm.resize(2 * nv * EYE_POINTS * 3);
+        a.d_eye_valid = eye_valid_.ptr;
+        a.d_eye_diam = eye_diam_.ptr;
+        a.d_eye_crop = eye_crop_.ptr;
+        a.d_eye_lm = eye_lm_.ptr;
+        a.d_out_eye_valid = sn.eye_valid.ptr;
+        a.d_out_eye_diam = sn.eye_diam.ptr;
+        a.d_out_eye_crop = sn.eye_crop.ptr;
+        a.d_out_eye_lm = sn.eye_lm.ptr;
+    }
+    check(zr_multi_export_async(&a, n_, K, L, stream_));
+    check(zr_memcpy_async(sn.h_small.ptr, sn.count.ptr, 4, 1, stream_));
+    check(zr_memcpy_async(sn.h_small.ptr + 1, sn.offsets.ptr, (n_ + 1) * 4, 1, stream_));
+    // the gallery's size as of this point of the stream: the rows the snapshot's identities can name
+    if (sn.enrol) check(zr_memcpy_async(sn.h_small.ptr + n_ + 2, enrol_->device_count(), 4, 1, stream_));
+    check(zr_event_record(sn.event, stream_));
+    sn.pending = true;
+}
+
+DeviceMultiTracker::PackedObjects DeviceMultiTracker::objects_packed() {
+    if (!snap_.pending) snapshot();
+    Snapshot &sn = snap_;
+    check(zr_event_synchronize(sn.event));
+    sn.pending = false;
+    const size_t K = (size_t)cfg_.slots, nv = n_ * K, L = (size_t)lm_net_.num_landmarks;
+    const size_t c = (size_t)std::min<int64_t>(std::max<int64_t>(sn.h_small[0], 0), (int64_t)nv);
+    PackedObjects out;
+    out.count = c;
+    out.num_landmarks = L;
+    out.stream_offsets = sn.h_small.ptr + 1;
+    // page-locked staging of the full size once, so the copies below never wait for an allocation
+    sn.h_header.resize(nv);
+    sn.h_lm.resize(nv * L * 3);
+    if (sn.pose) sn.h_pose.resize(nv);
+    if (sn.identity) {
+        sn.h_ident.resize(nv);
+        sn.h_emb.resize(nv * EMBEDDING_DIM);
+    }
+    if (sn.eyes) {
+        sn.h_eye_valid.resize(2 * nv);
+        sn.h_eye_diam.resize(2 * nv);
+        sn.h_eye_crop.resize(2 * nv * 5);
+        sn.h_eye_lm.resize(2 * nv * EYE_POINTS * 3);
+    }
+    if (c > 0) {
+        // the export is complete (the event), so a stream of the read-out's own does not queue
+        // behind the steps enqueued since
+        void *cs = sn.copy_stream;
+        check(zr_memcpy_async(sn.h_header.ptr, sn.header.ptr, c * sizeof(zr_export_header), 1, cs));
+        check(zr_memcpy_async(sn.h_lm.ptr, sn.lm.ptr, c * L * 3 * sizeof(float), 1, cs));
+        if (sn.pose) check(zr_memcpy_async(sn.h_pose.ptr, sn.pose_out.ptr, c * sizeof(zr_pose), 1, cs));
+        if (sn.identity) {
+            check(zr_memcpy_async(sn.h_ident.ptr, sn.ident.ptr, c * sizeof(zr_export_identity), 1, cs));
+            check(zr_memcpy_async(sn.h_emb.ptr, sn.emb.ptr, c * EMBEDDING_DIM * sizeof(float), 1, cs));
+        }
+        if (sn.eyes) {
+            check(zr_memcpy_async(sn.h_eye_valid.ptr, sn.eye_valid.ptr, 2 * c * 4, 1, cs));
+            check(zr_memcpy_async(sn.h_eye_diam.ptr, sn.eye_diam.ptr, 2 * c * 4, 1, cs));
+            check(zr_memcpy_async(sn.h_eye_crop.ptr, sn.eye_crop.ptr, 2 * c * 5 * 4, 1, cs));
+            check(zr_memcpy_async(sn.h_eye_lm.ptr, sn.eye_lm.ptr, 2 * c * EYE_POINTS * 3 * sizeof(float), 1, cs));
+        }
+        check(zr_stream_synchronize(cs));
+    }
+    out.headers = sn.h_header.ptr;
+    out.landmarks = sn.h_lm.ptr;
+    if (sn.pose) out.pose = sn.h_pose.ptr;
+    if (sn.identity) {
+        // the ids of the rows the steps up to the snapshot appended (objects()'s refresh, without
+        // reading a count that later steps may be moving)
+        if (sn.enrol && enrol_) enrol_->refresh_to(sn.h_small[n_ + 2]);
+        sn.person.assign(c, NO_MATCH);
+        for (size_t k = 0; k < c; k++)
+            if (gallery_ && (sn.h_header[k].flags & ZR_EXPORT_IDENTITY)) sn.person[k] = gallery_->id_of(sn.h_ident[k].row);
+        out.identity = sn.h_ident.ptr;
+        out.identity_id = sn.person.data();
+        out.embedding = sn.h_emb.ptr;
+    }
+    if (sn.eyes) {
+        out.eye_valid = sn.h_eye_valid.ptr;
+        out.iris_diameter = sn.h_eye_diam.ptr;
+        out.eye_crop = sn.h_eye_crop.ptr;
+        out.eye_landmarks = sn.h_eye_lm.ptr;
     }
     return out;
 }

@@ -179,6 +179,36 @@ class DeviceMultiTracker {
     };
     // after synchronize(): stream s's objects that have a result, in slot order
     std::vector<ObjectData> objects(size_t s);
+    // Every stream's objects at once (kernels/export.hip, zr_multi_export_async): what
+    // [objects(s) for every s] reports, gathered on the device into dense records in stream-then-slot
+    // order.  snapshot() enqueues, on the tracker's stream, the export into buffers of the snapshot's
+    // own, the copy of its count and stream offsets to page-locked memory, and an event; it does not
+    // wait, and steps enqueued after it do not change what it holds.  A later snapshot() replaces it,
+    // as do set_recognition and set_enrolment (they drop it).  Nothing of this runs, and nothing is
+    // allocated, unless snapshot() or objects_packed() is called.
+    void snapshot();
+    struct PackedObjects {
+        size_t count = 0;                           // objects with a result, over all streams
+        size_t num_landmarks = 0;                   // L
+        const int32_t *stream_offsets = nullptr;    // [streams + 1]: stream s owns records [off[s], off[s + 1])
+        const zr_export_header *headers = nullptr;  // [count] stream, slot, id, roi, confidence, flags
+        const float *landmarks = nullptr;           // [count][L][3]
+        // absent (nullptr) exactly where objects() leaves the field out
+        const zr_pose *pose = nullptr;                  // [count]
+        const zr_export_identity *identity = nullptr;   // [count]; flags & ZR_EXPORT_IDENTITY: embedded yet
+        const uint64_t *identity_id = nullptr;          // [count] Identity::id (NO_MATCH: unknown or none)
+        const float *embedding = nullptr;               // [count][128]
+        const int32_t *eye_valid = nullptr;             // [count][2] left, right
+        const float *iris_diameter = nullptr;           // [count][2]
+        const float *eye_crop = nullptr;                // [count][2][5]
+        const float *eye_landmarks = nullptr;           // [count][2][76][3]
+    };
+    // The pending snapshot's records, or -- none pending -- those of a snapshot taken now: waits for the
+    // snapshot's event only (not for steps enqueued since), then copies exactly `count` rows of each
+    // present array to page-locked staging on a stream of its own, with one wait: at most nine
+    // copies, however many streams.  The arrays are the tracker's and stay valid until the next
+    // objects_packed().  Consumes the snapshot.
+    PackedObjects objects_packed();
     std::vector<int32_t> object_counts();      // every stream's objects, with a result or new
     std::vector<int32_t> detection_pending();  // streams whose detection of the last step counts
     std::vector<int32_t> dropped_objects();    // per stream: the last step's new objects that found no free slot
@@ -251,6 +281,23 @@ class DeviceMultiTracker {
     DeviceArray<float> eye_crop_, eye_out_[2], eye_lm_, eye_diam_;
     DeviceArray<uint8_t> eye_atlas_;
     DeviceArray<uint64_t> eye_total_;
+    // the packed export: the snapshot's device records, its small page-locked read-back ([0] count,
+    // [1 ..] stream offsets, then the gallery's size with enrolment), and objects_packed()'s staging
+    struct Snapshot {
+        bool pending = false, pose = false, identity = false, eyes = false, enrol = false;
+        void *event = nullptr, *copy_stream = nullptr;
+        DeviceArray<int32_t> count, offsets, eye_valid;
+        DeviceArray<zr_export_header> header;
+        DeviceArray<float> lm, emb, eye_diam, eye_crop, eye_lm;
+        DeviceArray<zr_pose> pose_out;
+        DeviceArray<zr_export_identity> ident;
+        PinnedArray<int32_t> h_small, h_eye_valid;
+        PinnedArray<zr_export_header> h_header;
+        PinnedArray<float> h_lm, h_emb, h_eye_diam, h_eye_crop, h_eye_lm;
+        PinnedArray<zr_pose> h_pose;
+        PinnedArray<zr_export_identity> h_ident;
+        std::vector<uint64_t> person;
+    } snap_;
 };
 
 }  // namespace zh

@@ -159,6 +159,11 @@ void Gallery::refresh() {
     int32_t count = 0;
     check(zr_memcpy_async(&count, count_.ptr, sizeof count, 1, stream_));
     check(zr_stream_synchronize(stream_));
+    refresh_to(count);
+}
+
+void Gallery::refresh_to(int32_t count) {
+    if (!reserved_) return;
     const size_t have = ids_.size(), now = (size_t)std::min<int64_t>(std::max<int64_t>(count, 0), (int64_t)cap_);
     if (now <= have) return;  // rows are only ever appended
     ids_.resize(now);

@@ -82,6 +82,9 @@ class Gallery {
     bool reserved() const { return reserved_; }
     size_t capacity() const { return cap_; }
     void refresh();
+    // the mirror brought up to `count` rows the caller knows the device has completed (a count read
+    // behind an event, while later steps may still be appending: refresh() would read a count in flux)
+    void refresh_to(int32_t count);
     size_t enrolled() const { return enrolled_; }  // rows the device appended, as of the last refresh
     // every row read back from HBM: n * dim floats and n ids -- what a fresh gallery's add() takes
     void rows(std::vector<float> &out_rows, std::vector<uint64_t> &out_ids);

@@ -1427,6 +1427,77 @@ int zr_eye_commit_async(const zr_eye_cfg *cfg, size_t n, const int32_t *d_due_of
     });
 }
 
+// ---- every stream's tracked objects as one packed batch (kernels/export.hip)
+static_assert(sizeof(zr_export_header) == sizeof(zr::ExportHeader) && sizeof(zr_export_header) == 48,
+              "zr_export_header layout");
+static_assert(offsetof(zr_export_header, flags) == offsetof(zr::ExportHeader, flags), "zr_export_header layout");
+static_assert(sizeof(zr_export_identity) == sizeof(zr::ExportIdentity) && sizeof(zr_export_identity) == 16,
+              "zr_export_identity layout");
+static_assert(sizeof(zr_pose) == 4 * zr::EXPORT_POSE_WORDS, "zr_pose words");
+static_assert(3 * ZR_EYE_POINTS == zr::EXPORT_EYE_WORDS, "eye landmark words");
+static_assert(ZR_EXPORT_POSE == zr::EXPORT_POSE && ZR_EXPORT_IDENTITY == zr::EXPORT_IDENTITY &&
+                  ZR_EXPORT_EYE_LEFT == zr::EXPORT_EYE_LEFT && ZR_EXPORT_EYE_RIGHT == zr::EXPORT_EYE_RIGHT,
+              "export flags");
+
+int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_t slots, size_t num_landmarks,
+                          void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!a) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (!a->d_nobjects || !a->d_src || !a->d_ids || !a->d_roi || !a->d_state || !a->d_landmarks || !a->d_count ||
+            !a->d_stream_offsets || !a->d_header || !a->d_out_landmarks)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        const int pose = (a->d_pose != nullptr) + (a->d_out_pose != nullptr);
+        const int ident = (a->d_id_state != nullptr) + (a->d_id_emb != nullptr) + (a->d_out_identity != nullptr) +
+                          (a->d_out_emb != nullptr);
+        const int eyes = (a->d_eye_valid != nullptr) + (a->d_eye_diam != nullptr) + (a->d_eye_crop != nullptr) +
+                         (a->d_eye_lm != nullptr) + (a->d_out_eye_valid != nullptr) + (a->d_out_eye_diam != nullptr) +
+                         (a->d_out_eye_crop != nullptr) + (a->d_out_eye_lm != nullptr);
+        if ((pose != 0 && pose != 2) || (ident != 0 && ident != 4) || (eyes != 0 && eyes != 8))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "an optional group (pose, identity, eyes) is given in full or not at all");
+        if (n_streams == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "no streams");
+        if (slots == 0 || slots > 64) return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64");
+        if (num_landmarks == 0 || num_landmarks > (1u << 20))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "num_landmarks must be 1..2^20");
+        if (n_streams > (size_t)INT32_MAX / slots)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "streams x slots beyond the kernel's 32-bit record index");
+        zr::ExportParams p{};
+        p.nobjects = a->d_nobjects;
+        p.src = a->d_src;
+        p.ids = a->d_ids;
+        p.roi = a->d_roi;
+        p.state = reinterpret_cast<const zr::TrackState *>(a->d_state);
+        p.lm = reinterpret_cast<const uint32_t *>(a->d_landmarks);
+        p.pose = reinterpret_cast<const uint32_t *>(a->d_pose);
+        p.ist = reinterpret_cast<const zr::IdentityState *>(a->d_id_state);
+        p.emb = reinterpret_cast<const uint32_t *>(a->d_id_emb);
+        p.eye_valid = a->d_eye_valid;
+        p.eye_diam = reinterpret_cast<const uint32_t *>(a->d_eye_diam);
+        p.eye_crop = reinterpret_cast<const uint32_t *>(a->d_eye_crop);
+        p.eye_lm = reinterpret_cast<const uint32_t *>(a->d_eye_lm);
+        p.count = a->d_count;
+        p.offsets = a->d_stream_offsets;
+        p.header = reinterpret_cast<zr::ExportHeader *>(a->d_header);
+        p.out_lm = reinterpret_cast<uint32_t *>(a->d_out_landmarks);
+        p.out_pose = reinterpret_cast<uint32_t *>(a->d_out_pose);
+        p.out_ist = reinterpret_cast<zr::ExportIdentity *>(a->d_out_identity);
+        p.out_emb = reinterpret_cast<uint32_t *>(a->d_out_emb);
+        p.out_eye_valid = a->d_out_eye_valid;
+        p.out_eye_diam = reinterpret_cast<uint32_t *>(a->d_out_eye_diam);
+        p.out_eye_crop = reinterpret_cast<uint32_t *>(a->d_out_eye_crop);
+        p.out_eye_lm = reinterpret_cast<uint32_t *>(a->d_out_eye_lm);
+        p.S = (int)n_streams;
+        p.K = (int)slots;
+        p.L = (int)num_landmarks;
+        // 16-byte accesses only where every row of every array copied that way starts on 16 bytes
+        const uintptr_t bases = (uintptr_t)a->d_landmarks | (uintptr_t)a->d_out_landmarks | (uintptr_t)a->d_id_emb |
+                                (uintptr_t)a->d_out_emb | (uintptr_t)a->d_eye_lm | (uintptr_t)a->d_out_eye_lm;
+        p.vec4 = (3 * num_landmarks) % 4 == 0 && bases % 16 == 0 ? 1 : 0;
+        zr::launch_export(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 int zr_view_describe(const zr_view *views, size_t n, uint32_t frame, zr_view_desc *out) {
     return guarded([&]() -> int {
         if (!views || !out) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");

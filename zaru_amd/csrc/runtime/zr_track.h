@@ -311,6 +311,53 @@ struct EyeCommitParams {
 };
 const char *launch_eye_commit(const EyeCommitParams &p, hipStream_t s);
 
+// Every stream's objects that have a result as dense records (kernels/export.hip): slot j <
+// clamp(nobjects[s], 0, K) of stream s is exported iff r = src[s K + j] lies in [0, K); id, roi and
+// confidence come from slot j, everything else from slot r.  Layouts mirrored by zr_export_header /
+// zr_export_identity in include/zaru_hip.h.
+struct ExportHeader {
+    uint64_t id;
+    int32_t stream, slot;
+    float roi[5];
+    float confidence;
+    uint32_t flags;  // EXPORT_*
+    uint32_t reserved;
+};
+struct ExportIdentity {
+    int32_t row;
+    float distance;
+    uint32_t embeddings, flags;
+};
+enum { EXPORT_POSE = 1, EXPORT_IDENTITY = 2, EXPORT_EYE_LEFT = 4, EXPORT_EYE_RIGHT = 8 };
+enum { EXPORT_POSE_WORDS = 21, EXPORT_EYE_WORDS = 228 };  // zr_pose; 76 x 3 eye landmarks
+struct ExportParams {
+    const int32_t *nobjects;     // [S]
+    const int32_t *src;          // [S * K]
+    const uint64_t *ids;         // [S * K]
+    const float *roi;            // [S * K][5]
+    const TrackState *state;     // [S * K]
+    const uint32_t *lm;          // [S * K][3 L]
+    const uint32_t *pose;        // [S * K][21], null: no pose
+    const IdentityState *ist;    // [S * K], null: no identity
+    const uint32_t *emb;         // [S * K][IDENTITY_DIM]
+    const int32_t *eye_valid;    // [2 S K], null: no eyes
+    const uint32_t *eye_diam;    // [2 S K]
+    const uint32_t *eye_crop;    // [2 S K][5]
+    const uint32_t *eye_lm;      // [2 S K][228]
+    int32_t *count;              // out
+    int32_t *offsets;            // [S + 1] out
+    ExportHeader *header;        // [S * K] out: the first *count records, as every array below
+    uint32_t *out_lm;
+    uint32_t *out_pose;
+    ExportIdentity *out_ist;
+    uint32_t *out_emb;
+    int32_t *out_eye_valid;
+    uint32_t *out_eye_diam, *out_eye_crop, *out_eye_lm;
+    int S, K, L;
+    int vec4;                    // 3 L % 4 == 0 and lm, emb, eye_lm and their outputs 16-byte aligned
+};
+const char *launch_export(const ExportParams &p, hipStream_t s);
+
 // fn: 0 sinf, 1 cosf, 2 expf, 3 atanf, 4 atan2f(a, b) -- glibc_math.h on the device
 const char *launch_glibc_math(int fn, const float *a, const float *b, float *out, int64_t n, hipStream_t s);
 
