@@ -140,6 +140,34 @@ int zr_detect_post_mapped_async(const float *d_logits, const float *d_boxes, con
                                 const zr_detpost_cfg *cfg, int32_t *d_count, float *d_dets, size_t dcap,
                                 int32_t *d_ties, void *hip_stream);
 
+/* Tiled detection's merge.  The detector ran on T views (tiles) of each due stream and
+ * zr_detect_post_mapped_async wrote tile t of stream s to slot s * T + t of d_tile_count [n * T] /
+ * d_tile_dets [n * T][tile_cap][20], in frame pixels (one letterbox row per tile).  For each due
+ * stream s = d_due[k], k < *d_ndue (clamped to n), one wave builds the union of its tiles' lists in
+ * tile order -- within a tile the first min(count, tile_cap) records, counts read clamped to
+ * 0..tile_cap -- and puts it through NonMaxSuppression::process (nms.rs:59-145) once more, with
+ * cfg's mode and IoU threshold, as the post-processing above restates it: ascending stable sort by
+ * total_cmp of the confidence (ties keep union order), seeds popped from the top; Average:
+ * confidence of the seed, every other field weighted by confidence, summed seed first then in
+ * retained order, divided by the summed confidence; Remove: the seed as it is; a NaN IoU decides as
+ * the comparisons do.  Written: d_count[s] (exact, whatever dcap is), the first dcap records of
+ * d_dets [n][dcap][20] (fields past `keypoints` keypoints are 0), d_ties[2 s ..] = {union size,
+ * members sharing their confidence} (may be NULL; above 20 candidates a tie's order is not pinned by
+ * the reference, as above) and d_tile_dropped[s] = sum over tiles of max(count - tile_cap, 0) (may
+ * be NULL).  Streams that are not due are not touched.
+ * Refused (ZR_ERR_INVALID_ARGUMENT, nothing launched): a NULL required pointer, n == 0, tiles
+ * outside 1..16, tile_cap outside 1..256, tiles * tile_cap > 1024, keypoints outside 0..7, a mode
+ * other than 0 / 1, dcap == 0. */
+typedef struct {
+    int tiles, tile_cap;    /* T, records kept per tile */
+    int keypoints;          /* the detector's (6 / 7) */
+    float iou;              /* NMS IoU threshold */
+    int mode;               /* SuppressionMode: 0 Average, 1 Remove */
+} zr_detmerge_cfg;
+int zr_detect_merge_async(const int32_t *d_tile_count, const float *d_tile_dets, const int32_t *d_due,
+                          const int32_t *d_ndue, size_t n, const zr_detmerge_cfg *cfg, int32_t *d_count,
+                          float *d_dets, size_t dcap, int32_t *d_ties, int32_t *d_tile_dropped, void *hip_stream);
+
 /* ---- Face recognition: embedding matching --------------------------------------------------
  * Embedding::difference (examples/eval_face_recognition.rs:31-42) of every query against every
  * gallery row, and each query's nearest row.  d_query is [q][dim] and d_gallery [g][dim] f32,
@@ -489,6 +517,17 @@ int zr_cnn_estimate_device_views_count_async(zr_session *s, const zr_frame *fram
  * d_total (may be NULL): *d_total += *d_ndue, a running count of the detections run. */
 int zr_due_compact_async(const int32_t *d_det_pending, size_t n, const zr_view_desc *view_template, int32_t *d_due,
                          int32_t *d_ndue, zr_view_desc *d_due_views, uint64_t *d_total, void *hip_stream);
+/* The same scan with `tiles` (1..16) detector views per due stream, for tiled detection: d_due[k] =
+ * s and *d_ndue as above, and for t < tiles d_due_slots[k * tiles + t] = s * tiles + t (the map of
+ * zr_detect_post_mapped_async) and d_due_views[k * tiles + t] = d_tile_templates[t] (device
+ * memory) with its frame index set to s; *d_nviews = *d_ndue * tiles.  d_total_streams /
+ * d_total_views (may be NULL): += *d_ndue / *d_nviews.  Entries at and past the counts are not
+ * written.  Refused (ZR_ERR_INVALID_ARGUMENT, nothing launched): a NULL required pointer, n == 0,
+ * tiles outside 1..16. */
+int zr_due_compact_tiles_async(const int32_t *d_det_pending, size_t n, const zr_view_desc *d_tile_templates,
+                               size_t tiles, int32_t *d_due, int32_t *d_ndue, int32_t *d_due_slots,
+                               zr_view_desc *d_due_views, int32_t *d_nviews, uint64_t *d_total_streams,
+                               uint64_t *d_total_views, void *hip_stream);
 /* The face video loop of the reference's demo (crates/zaru/examples/facemesh.rs:35-56: track, and
  * on loss detect on the same frame and re-seed the tracker from the most confident detection) on
  * the device, in two calls around a mapped detection (zr_cnn_estimate_device_views_count_async +

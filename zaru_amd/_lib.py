@@ -55,6 +55,12 @@ class MultiCfg(C.Structure):
                 ("interval_ms", C.c_double), ("aspect_w", C.c_int), ("aspect_h", C.c_int)]
 
 
+class DetMergeCfg(C.Structure):
+    """zr_detmerge_cfg: tiled detection's merge (zr_detect_merge_async); mode 0 Average, 1 Remove."""
+    _fields_ = [("tiles", C.c_int), ("tile_cap", C.c_int), ("keypoints", C.c_int), ("iou", C.c_float),
+                ("mode", C.c_int)]
+
+
 class LmFilter(C.Structure):
     """zr_lm_filter: kind 0 none, 1 EMA {alpha}, 2 alpha-beta {alpha, beta}, 3 1 euro
     {min_cutoff, beta, d_cutoff}."""
@@ -160,6 +166,8 @@ SIGNATURES = [
     ("zr_detect_post_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _U32, _U32, _P, _P]),
     ("zr_detect_post_mapped_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     ("zr_due_compact_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("zr_due_compact_tiles_async", _I, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("zr_detect_merge_async", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _P, _P]),
     ("zr_track_lost_compact_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_track_reseed_best_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_cnn_estimate_device_views_count_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _F, _F, _P, _P]),

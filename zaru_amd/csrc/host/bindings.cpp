@@ -291,6 +291,28 @@ PYBIND11_MODULE(_zaru_host, m) {
             return d.detect(host_image(img));
         });
 
+    // tiled detection (host/detection.h): the grid, and the host oracle of the device path
+    m.def("detection_tiles", &detection_tiles, py::arg("width"), py::arg("height"), py::arg("cols"), py::arg("rows"),
+          py::arg("overlap") = 0.25f, py::arg("include_full") = true);
+    py::class_<TiledDetector>(m, "TiledDetector")
+        .def(py::init([](const std::string &net, const std::vector<Rect> &tiles, int device) {
+                 return new TiledDetector(detector_net(net), tiles, device);
+             }), py::arg("network"), py::arg("tiles"), py::arg("device") = 0)
+        .def("set_threshold", &TiledDetector::set_threshold)
+        .def("set_nms_iou", [](TiledDetector &d, float t) { d.nms_mut().set_iou_thresh(t); })
+        .def("set_nms_mode", [](TiledDetector &d, SuppressionMode m) { d.nms_mut().set_mode(m); })
+        .def("set_tile_cap", &TiledDetector::set_tile_cap, py::arg("tile_cap"))
+        .def("tile_cap", &TiledDetector::tile_cap)
+        .def("tiles", &TiledDetector::tiles)
+        .def("tile_detections", [](TiledDetector &d, py::array_t<uint8_t, py::array::c_style> img) {
+            return d.tile_detections(host_image(img));
+        })
+        .def("detect", [](TiledDetector &d, py::array_t<uint8_t, py::array::c_style> img) {
+            return d.detect(host_image(img));
+        })
+        .def("ties", [](const TiledDetector &d) { return std::make_pair(d.ties().candidates, d.ties().tied); })
+        .def("dropped", &TiledDetector::dropped);
+
     // crates/zaru/src/filter: the parameters of the three landmark filters, and LandmarkFilter
     // (landmark.rs:142-202) usable alone on (L, 3) float32 arrays
     py::class_<Ema>(m, "Ema").def(py::init<float>(), py::arg("alpha")).def_readonly("alpha", &Ema::alpha);
@@ -488,6 +510,12 @@ PYBIND11_MODULE(_zaru_host, m) {
             t.set_pose_reference(pose_reference_arg(points), flip_y);
         }, py::arg("points"), py::arg("flip_y") = true)
         .def("inject_detections", &DeviceMultiTracker::inject_detections)
+        // tiled detection: the detector on every rect (frame px), merged on the device; [] turns it off
+        .def("set_detection_tiles", &DeviceMultiTracker::set_detection_tiles, py::arg("rects"),
+             py::arg("tile_cap") = DEFAULT_TILE_CAP)
+        .def("detection_tiles", &DeviceMultiTracker::detection_tiles)
+        .def("detector_views", &DeviceMultiTracker::detector_views)
+        .def("dropped_tile_detections", &DeviceMultiTracker::dropped_tile_detections)
         .def("step", [](DeviceMultiTracker &t, const std::vector<std::tuple<uint64_t, uint32_t, uint32_t, uint64_t>> &frames,
                         double now_ms, std::optional<float> elapsed) {
             const std::vector<Image> im = device_frames(frames);

@@ -230,4 +230,84 @@ const std::vector<Detection> &Detector::detect(const Image &img) {
     return dets_;
 }
 
+void check_detection_tiles(size_t tiles, uint32_t tile_cap) {
+    if (tiles < 1 || tiles > MAX_DETECTION_TILES) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "detection tiles: 1..16 rects");
+    if (tile_cap < 1 || tile_cap > MAX_TILE_CAP) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "tile_cap must be 1..256");
+    if (tiles * tile_cap > MAX_TILE_UNION)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "tiles x tile_cap must be <= 1024");
+}
+
+std::vector<Rect> detection_tiles(uint32_t W, uint32_t H, uint32_t cols, uint32_t rows, float overlap,
+                                  bool include_full) {
+    if (cols == 0 || rows == 0) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "detection_tiles: cols and rows must be >= 1");
+    if (!(overlap >= 0.f && overlap < 1.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "detection_tiles: overlap must be in [0, 1)");
+    if ((uint64_t)cols * rows + (include_full ? 1 : 0) > MAX_DETECTION_TILES)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "detection_tiles: more than 16 rects");
+    const float fw = (float)W, fh = (float)H;
+    const float tw = fw / ((float)cols - (float)(cols - 1) * overlap), th = fh / ((float)rows - (float)(rows - 1) * overlap);
+    const float sx = tw * (1.f - overlap), sy = th * (1.f - overlap);
+    std::vector<Rect> out;
+    if (include_full) out.push_back(Rect::from_top_left(0.f, 0.f, fw, fh));
+    for (uint32_t r = 0; r < rows; r++)
+        for (uint32_t c = 0; c < cols; c++) {
+            const float x0 = c + 1 == cols ? fw - tw : (float)c * sx;  // the last column / row ends at the edge
+            const float y0 = r + 1 == rows ? fh - th : (float)r * sy;
+            out.push_back(Rect::from_top_left(x0, y0, tw, th));
+        }
+    return out;
+}
+
+std::vector<ViewData> tile_views(uint32_t W, uint32_t H, const std::vector<Rect> &tiles, AspectRatio in_aspect,
+                                 std::vector<Rect> *rects_out) {
+    const ViewData full = ViewData::full(W, H);
+    std::vector<ViewData> views;
+    if (rects_out) rects_out->clear();
+    for (const Rect &t : tiles) {
+        const Rect rect = t.grow_to_fit_aspect(in_aspect);
+        if (rects_out) rects_out->push_back(rect);
+        views.push_back(full.view(RotatedRect(rect, 0.f)));
+    }
+    return views;
+}
+
+TiledDetector::TiledDetector(DetectorNetwork net, std::vector<Rect> tiles, int device)
+    : net_(std::move(net)), tiles_(std::move(tiles)) {
+    check_detection_tiles(tiles_.size(), cap_);
+    cnn_ = network_cnn(net_.kind, device);
+}
+
+void TiledDetector::set_tile_cap(uint32_t cap) {
+    check_detection_tiles(tiles_.size(), cap);
+    cap_ = cap;
+}
+
+std::vector<std::vector<Detection>> TiledDetector::tile_detections(const Image &img) {
+    std::vector<Rect> rects;
+    const std::vector<ViewData> views = tile_views(img.width, img.height, tiles_, cnn_->aspect(), &rects);
+    auto outs = cnn_->estimate(img, views);
+    const size_t A = net_.anchors().size();
+    std::vector<std::vector<Detection>> per(tiles_.size());
+    for (size_t t = 0; t < tiles_.size(); t++) {
+        std::vector<Detection> raw;
+        net_.extract(outs[0].data() + t * A * net_.params, outs[1].data() + t * A, thresh_, cnn_->input_width(),
+                     cnn_->input_height(), raw);
+        per[t] = nms_.process(raw);
+        map_detections(per[t], rects[t], cnn_->input_width());
+    }
+    return per;
+}
+
+const std::vector<Detection> &TiledDetector::detect(const Image &img) {
+    const auto per = tile_detections(img);
+    std::vector<Detection> all;
+    dropped_ = 0;
+    for (const auto &p : per) {
+        const size_t c = std::min<size_t>(p.size(), cap_);
+        all.insert(all.end(), p.begin(), p.begin() + c);
+        dropped_ += (uint32_t)(p.size() - c);
+    }
+    dets_ = nms_.process(all, &ties_);
+    return dets_;
+}
+
 }  // namespace zh

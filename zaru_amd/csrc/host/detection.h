@@ -105,6 +105,66 @@ class Detector {  // detection.rs:152-276
 // The letterboxed view a detector samples from a w x h image (detection.rs:224-227).
 ViewData letterbox_view(uint32_t w, uint32_t h, AspectRatio in_aspect, Rect *rect_out = nullptr);
 
+// ---- Tiled detection: the detector on overlapping tiles of the frame, merged ----------------
+// The reference has no tiling; this is the composition of two of its operations, Detector::detect
+// on a view of the image and NonMaxSuppression::process on a list of detections:
+//   1. per tile t (any rect in frame pixels, in order; it may reach outside the frame) the
+//      detector's view is tile.grow_to_fit_aspect(detector aspect) -- detection.rs:224-227's
+//      letterbox rule on the tile rect instead of the image rect -- and sample, infer,
+//      extract_outputs, NMS and map_detections run as in Detector::detect, the map with that rect as
+//      the letterbox, so the tile's detections come out in frame pixels.  (Deviation:
+//      detect(&image.view(tile)) would return view-local coordinates, and a caller adding the
+//      tile's corner afterwards rounds twice; here the map is applied once.)
+//   2. the union -- tile order, within a tile its output order (most confident first), at most
+//      tile_cap per tile -- goes through NonMaxSuppression::process once more, same mode and
+//      threshold.  Ties keep union order.
+// Known limit: a face cut by a tile border gives a partial box in that tile; when its IoU with the
+// whole box from the neighbouring tile is below the threshold both survive the merge (a tracker's
+// RoI sweep removes one).  The overlap should be at least the largest face the tiles are meant to
+// find; larger faces are the full-frame tile's job.
+constexpr size_t MAX_DETECTION_TILES = 16;
+constexpr uint32_t DEFAULT_TILE_CAP = 64, MAX_TILE_CAP = 256, MAX_TILE_UNION = 1024;
+// what zr_detect_merge_async accepts; throws ZR_ERR_INVALID_ARGUMENT otherwise
+void check_detection_tiles(size_t tiles, uint32_t tile_cap);
+
+// A cols x rows grid over a W x H frame: tile width W / (cols - (cols - 1) * overlap), stride
+// width * (1 - overlap) (height likewise), the last column and row placed against the frame's
+// edge.  Order: the full frame first when included, then row-major.  Refused: cols or rows of 0,
+// an overlap outside [0, 1), more than 16 rects.
+std::vector<Rect> detection_tiles(uint32_t W, uint32_t H, uint32_t cols, uint32_t rows, float overlap = 0.25f,
+                                  bool include_full = true);
+
+// The detector's views of the tiles in a W x H image, and (optional) the letterbox rect of each.
+std::vector<ViewData> tile_views(uint32_t W, uint32_t H, const std::vector<Rect> &tiles, AspectRatio in_aspect,
+                                 std::vector<Rect> *rects_out = nullptr);
+
+class TiledDetector {  // the host oracle of DeviceMultiTracker::set_detection_tiles
+  public:
+    TiledDetector(DetectorNetwork net, std::vector<Rect> tiles, int device = 0);
+    void set_threshold(float t) { thresh_ = t; }
+    float threshold() const { return thresh_; }
+    NonMaxSuppression &nms_mut() { return nms_; }
+    void set_tile_cap(uint32_t cap);
+    uint32_t tile_cap() const { return cap_; }
+    const std::vector<Rect> &tiles() const { return tiles_; }
+    // every tile's own list, in frame pixels, uncapped (the T views go through the Cnn in one batch)
+    std::vector<std::vector<Detection>> tile_detections(const Image &img);
+    const std::vector<Detection> &detect(const Image &img);
+    // of the last detect(): the merge's candidates / ties, and detections past tile_cap, summed
+    NonMaxSuppression::TieCount ties() const { return ties_; }
+    uint32_t dropped() const { return dropped_; }
+
+  private:
+    DetectorNetwork net_;
+    std::shared_ptr<const Cnn> cnn_;
+    std::vector<Rect> tiles_;
+    uint32_t cap_ = DEFAULT_TILE_CAP, dropped_ = 0;
+    float thresh_ = Detector::DEFAULT_THRESHOLD;
+    NonMaxSuppression nms_;
+    NonMaxSuppression::TieCount ties_;
+    std::vector<Detection> dets_;
+};
+
 // Conservative raw-logit bound below which sigmoid(logit) < thresh for sure; used by the
 // device candidate compaction so that the exact host decode sees every anchor it could keep.
 float candidate_logit_floor(float thresh);

@@ -140,6 +140,62 @@ void DeviceMultiTracker::set_roi_padding(float p) {
     tcfg_.padding = p;
 }
 
+void DeviceMultiTracker::set_detection_tiles(const std::vector<Rect> &rects, uint32_t tile_cap) {
+    if (rects.empty()) {  // off: the next step's detector runs on the whole frame again
+        tiles_.clear();
+        return;
+    }
+    check_detection_tiles(rects.size(), tile_cap);
+    synchronize();  // the last step's launches still read the detector's buffers
+    const size_t T = rects.size(), nt = n_ * T;
+    tile_tmpl_.resize(T);
+    tile_views_.resize(nt);
+    tile_slots_.resize(nt);
+    tile_count_.resize(nt);
+    tile_lbox_.resize(4 * nt);
+    tile_dets_.resize(nt * tile_cap * 20);
+    det_boxes_.resize(nt * (size_t)pcfg_.anchors * pcfg_.params);
+    det_logits_.resize(nt * (size_t)pcfg_.anchors);
+    nviews_.resize(1);
+    if (!views_total_.ptr) {
+        views_total_.resize(1);
+        tile_dropped_.resize(n_);
+        check(zr_memset_async(views_total_.ptr, 0, 8, stream_));
+        check(zr_memset_async(tile_dropped_.ptr, 0, n_ * 4, stream_));
+    }
+    check(zr_memset_async(nviews_.ptr, 0, 4, stream_));
+    check(zr_stream_synchronize(stream_));
+    tiles_ = rects;
+    tile_cap_ = tile_cap;
+    if (fw_) reset_tile_views();
+}
+
+// The tiles' template views and letterbox rows at this frame size, and a valid view in every entry
+// of the packed table, as frame_size() does for the others.
+void DeviceMultiTracker::reset_tile_views() {
+    const size_t T = tiles_.size(), nt = n_ * T;
+    std::vector<Rect> lb;
+    const std::vector<ViewData> vd = tile_views(fw_, fh_, tiles_, det_->aspect(), &lb);
+    std::vector<zr_view> zv(T);
+    for (size_t t = 0; t < T; t++) zv[t] = to_zr_view(vd[t]);
+    std::vector<zr_view_desc> tmpl(T), all(nt);
+    check(zr_view_describe(zv.data(), T, 0, tmpl.data()));
+    std::vector<float> l(4 * nt);
+    for (size_t i = 0; i < nt; i++) {
+        const size_t t = i % T;
+        all[i] = tmpl[t];
+        all[i].frame = (uint32_t)(i / T);
+        l[4 * i] = lb[t].center().x;
+        l[4 * i + 1] = lb[t].center().y;
+        l[4 * i + 2] = lb[t].width();
+        l[4 * i + 3] = lb[t].height();
+    }
+    check(zr_memcpy_async(tile_tmpl_.ptr, tmpl.data(), T * sizeof(zr_view_desc), 0, stream_));
+    check(zr_memcpy_async(tile_views_.ptr, all.data(), nt * sizeof(zr_view_desc), 0, stream_));
+    check(zr_memcpy_async(tile_lbox_.ptr, l.data(), l.size() * 4, 0, stream_));
+    check(zr_stream_synchronize(stream_));  // the host vectors are pageable and go out of scope
+}
+
 void DeviceMultiTracker::set_pose_reference(const std::vector<float> &points, bool flip_y) {
     pose_.set(points, flip_y, (size_t)lm_net_.num_landmarks, stream_);
 }
@@ -403,6 +459,7 @@ void DeviceMultiTracker::frame_size(uint32_t W, uint32_t H) {
     check(zr_memcpy_async(dense_views_.ptr, dense.data(), nv * sizeof(zr_view_desc), 0, stream_));
     check(zr_stream_synchronize(stream_));
     if (embedder_) reset_identity_views();
+    if (!tiles_.empty()) reset_tile_views();
 }
 
 // injected detections go ahead of the detector's result that this step consumes (test hook; the
@@ -519,13 +576,28 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
     // 6. the detector (Detector::detect_impl, detection.rs:224-267) on the streams step 3 asked to
     // detect on, taken next step: their list and count stay on the device
     float *dd[2] = {det_boxes_.ptr, det_logits_.ptr};
-    check(zr_due_compact_async(det_pending_.ptr, n_, &det_tmpl_, due_.ptr, ndue_.ptr, due_views_.ptr, due_total_.ptr,
-                               stream_));
     const ColorMapper dc = det_->color_mapper();
-    check(zr_cnn_estimate_device_views_count_async(det_->nn().handle(), zf.data(), n_, due_views_.ptr, n_, ndue_.ptr,
-                                                   dc.lo, dc.hi, dd, stream_));
-    check(zr_detect_post_mapped_async(det_logits_.ptr, det_boxes_.ptr, anchors_.ptr, lbox_.ptr, n_, due_.ptr, ndue_.ptr,
-                                      &pcfg_, count_.ptr, dets_.ptr, dcap_, nullptr, stream_));
+    if (!tiles_.empty()) {
+        // tiled: T views per due stream, each tile's list in frame px, merged into count_ / dets_
+        const size_t T = tiles_.size(), nt = n_ * T;
+        check(zr_due_compact_tiles_async(det_pending_.ptr, n_, tile_tmpl_.ptr, T, due_.ptr, ndue_.ptr, tile_slots_.ptr,
+                                         tile_views_.ptr, nviews_.ptr, due_total_.ptr, views_total_.ptr, stream_));
+        check(zr_cnn_estimate_device_views_count_async(det_->nn().handle(), zf.data(), n_, tile_views_.ptr, nt,
+                                                       nviews_.ptr, dc.lo, dc.hi, dd, stream_));
+        check(zr_detect_post_mapped_async(det_logits_.ptr, det_boxes_.ptr, anchors_.ptr, tile_lbox_.ptr, nt,
+                                          tile_slots_.ptr, nviews_.ptr, &pcfg_, tile_count_.ptr, tile_dets_.ptr,
+                                          tile_cap_, nullptr, stream_));
+        const zr_detmerge_cfg mc{(int)T, (int)tile_cap_, pcfg_.keypoints, pcfg_.iou, pcfg_.mode};
+        check(zr_detect_merge_async(tile_count_.ptr, tile_dets_.ptr, due_.ptr, ndue_.ptr, n_, &mc, count_.ptr, dets_.ptr,
+                                    dcap_, nullptr, tile_dropped_.ptr, stream_));
+    } else {
+        check(zr_due_compact_async(det_pending_.ptr, n_, &det_tmpl_, due_.ptr, ndue_.ptr, due_views_.ptr,
+                                   due_total_.ptr, stream_));
+        check(zr_cnn_estimate_device_views_count_async(det_->nn().handle(), zf.data(), n_, due_views_.ptr, n_,
+                                                       ndue_.ptr, dc.lo, dc.hi, dd, stream_));
+        check(zr_detect_post_mapped_async(det_logits_.ptr, det_boxes_.ptr, anchors_.ptr, lbox_.ptr, n_, due_.ptr,
+                                          ndue_.ptr, &pcfg_, count_.ptr, dets_.ptr, dcap_, nullptr, stream_));
+    }
     steps_++;
 }
 
@@ -559,6 +631,10 @@ std::vector<int32_t> DeviceMultiTracker::dropped_detections() {
 }
 
 uint64_t DeviceMultiTracker::detector_frames() { return read_u64(due_total_); }
+uint64_t DeviceMultiTracker::detector_views() { return views_total_.ptr ? read_u64(views_total_) : 0; }
+std::vector<int32_t> DeviceMultiTracker::dropped_tile_detections() {
+    return tile_dropped_.ptr ? read_i32(tile_dropped_) : std::vector<int32_t>(n_, 0);
+}
 uint64_t DeviceMultiTracker::landmark_images() { return read_u64(lm_total_) + uncompacted_; }
 uint64_t DeviceMultiTracker::identity_images() { return id_total_.ptr ? read_u64(id_total_) : 0; }
 uint64_t DeviceMultiTracker::enrolled_total() {

@@ -18,6 +18,11 @@
 //   5. the landmark network on exactly those views (zr_cnn_estimate_device_views_count_async),
 //   6. the detector on the streams step 3 asked to detect on, as DeviceHandTracker runs BlazePalm
 //      (zr_due_compact_async, the counted launches, zr_detect_post_mapped_async).
+//      With detection tiles set (set_detection_tiles; host/detection.h has the semantics) step 6 is
+//      zr_due_compact_tiles_async (T views per due stream), the counted launches on streams x T
+//      views, zr_detect_post_mapped_async over streams x T rows with one letterbox row per tile and
+//      tile_cap records each, and zr_detect_merge_async into the same count / list: steps 1-5 and
+//      everything that reads the detections see no difference.
 // Schedule: a detection requested at step t is taken at step t + 1 (DeviceHandTracker's).
 // Face detectors start an object on the detection's bounding rect, unrotated and with the
 // LandmarkTracker's default padding (examples/facemesh.rs:49-54); the palm detector with
@@ -89,6 +94,15 @@ class DeviceMultiTracker {
     // A/B switch (default on): off runs the landmark network on all streams x slots views each
     // step, idle slots included (DeviceHandTracker's schedule).  The results are the same bits.
     void set_compact(bool on) { compact_ = on; }
+    // Tiled detection (default off: an empty list): the detector runs on every rect of `rects` (frame
+    // pixels, e.g. detection_tiles(); the same for every stream) and the tiles' detections are merged
+    // on the device (TiledDetector in host/detection.h is the oracle).  Allowed between steps: it
+    // takes effect with the next step's detector run, and the previous step's pending result is
+    // consumed as it is.  Off, a step enqueues exactly what it did without.  Refuses what
+    // zr_detect_merge_async refuses: more than 16 rects, tile_cap outside 1..256, rects x tile_cap
+    // above 1024.
+    void set_detection_tiles(const std::vector<Rect> &rects, uint32_t tile_cap = DEFAULT_TILE_CAP);
+    const std::vector<Rect> &detection_tiles() const { return tiles_; }
     // head pose of every object against `points` (n x 3 floats, e.g. the canonical face mesh; empty:
     // off, the default), as DeviceFaceLoop::set_pose_reference
     void set_pose_reference(const std::vector<float> &points, bool flip_y = true);
@@ -215,6 +229,9 @@ class DeviceMultiTracker {
     std::vector<int32_t> dropped_detections(); // per stream: detections past the detection capacity
     size_t detection_capacity() const { return dcap_; }
     uint64_t detector_frames();   // frames the detector ran on, summed over the steps
+    uint64_t detector_views();    // tile views the detector ran on, summed over the tiled steps
+    // per stream: its last tiled detection's records past tile_cap, summed over the tiles
+    std::vector<int32_t> dropped_tile_detections();
     uint64_t landmark_images();   // views the landmark network ran on, summed over the steps
     uint64_t identity_images();   // embeddings made, summed over the steps (0 before set_recognition)
     uint64_t eye_images();        // views the eye network ran on, summed over the steps
@@ -222,6 +239,7 @@ class DeviceMultiTracker {
   private:
     void frame_size(uint32_t W, uint32_t H);
     void apply_injected();
+    void reset_tile_views();
     void identify(const std::vector<zr_frame> &zf, double now_ms);
     void reset_identity_views();
     void refine_eyes(const std::vector<zr_frame> &zf);
@@ -251,6 +269,14 @@ class DeviceMultiTracker {
     DeviceArray<int32_t> due_, ndue_;
     zr_view_desc det_tmpl_{};  // the letterboxed detector view (frame index set per stream)
     DeviceArray<uint64_t> due_total_, lm_total_;
+    // tiled detection: the tiles' template views, the packed views x T table with its slot map and
+    // count, the per-tile letterbox rows, and the per-tile lists the merge reads
+    std::vector<Rect> tiles_;
+    uint32_t tile_cap_ = DEFAULT_TILE_CAP;
+    DeviceArray<zr_view_desc> tile_tmpl_, tile_views_;
+    DeviceArray<int32_t> tile_slots_, nviews_, tile_count_, tile_dropped_;
+    DeviceArray<float> tile_lbox_, tile_dets_;
+    DeviceArray<uint64_t> views_total_;
     DevicePose pose_;
     DeviceFilter filter_;                 // two state buffers of streams x slots rows
     std::optional<float> prev_elapsed_;   // the previous step's `elapsed`: its estimates' (nullopt: dt)

@@ -330,9 +330,10 @@ __global__ __launch_bounds__(64) void hand_manage_kernel(const HandManageParams 
 
 // one workgroup: a block-wide exclusive scan of the request flags per 1024-stream chunk; the
 // flags are pending[s] != 0, or (lost_of != null) the streams whose tracker holds no RoI
-__global__ __launch_bounds__(1024) void due_compact_kernel(const int32_t *pending, const TrackState *lost_of, int S,
-                                                           const ViewDesc tmpl, int32_t *due, int32_t *ndue,
-                                                           ViewDesc *due_views, uint64_t *total) {
+// (the scan, shared by the two kernels below: emit(k, s) for the k-th requesting stream s, in
+// stream order; returns their number, to every thread)
+template <class Emit>
+__device__ __forceinline__ int due_scan(const int32_t *pending, const TrackState *lost_of, int S, Emit emit) {
     __shared__ int wsum[16];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     int base = 0;
@@ -348,20 +349,51 @@ __global__ __launch_bounds__(1024) void due_compact_kernel(const int32_t *pendin
             before += i < w ? wsum[i] : 0;
             total += wsum[i];
         }
-        if (req) {
-            const int k = base + before + in_wave;
-            due[k] = s;
-            ViewDesc v = tmpl;
-            v.frame = (uint32_t)s;
-            due_views[k] = v;
-        }
+        if (req) emit(base + before + in_wave, s);
         base += total;
         __syncthreads();  // wsum is rewritten by the next chunk
     }
-    if (t == 0) {
+    return base;
+}
+
+__global__ __launch_bounds__(1024) void due_compact_kernel(const int32_t *pending, const TrackState *lost_of, int S,
+                                                           const ViewDesc tmpl, int32_t *due, int32_t *ndue,
+                                                           ViewDesc *due_views, uint64_t *total) {
+    const int base = due_scan(pending, lost_of, S, [=](int k, int s) {
+        due[k] = s;
+        ViewDesc v = tmpl;
+        v.frame = (uint32_t)s;
+        due_views[k] = v;
+    });
+    if (threadIdx.x == 0) {
         *ndue = base;
         if (total) *total += (uint64_t)base;
     }
+}
+
+// the same scan with T views per requesting stream (tiled detection): slot s * T + t and tile t's
+// template view with frame = s at k * T + t
+__global__ __launch_bounds__(1024) void due_compact_tiles_kernel(const DueTilesParams P) {
+    const int base = due_scan(P.pending, nullptr, P.S, [=](int k, int s) {
+        P.due[k] = s;
+        for (int t = 0; t < P.T; ++t) {
+            ViewDesc v = P.tmpl[t];
+            v.frame = (uint32_t)s;
+            P.due_slots[(int64_t)k * P.T + t] = s * P.T + t;
+            P.due_views[(int64_t)k * P.T + t] = v;
+        }
+    });
+    if (threadIdx.x == 0) {
+        *P.ndue = base;
+        *P.nviews = base * P.T;
+        if (P.total_streams) *P.total_streams += (uint64_t)base;
+        if (P.total_views) *P.total_views += (uint64_t)base * (uint64_t)P.T;
+    }
+}
+
+const char *launch_due_compact_tiles(const DueTilesParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(due_compact_tiles_kernel, dim3(1), dim3(1024), 0, s, p);
+    return "due_compact_tiles_kernel";
 }
 
 const char *launch_due_compact(const int32_t *det_pending, const TrackState *lost_of, int S, const ViewDesc &tmpl,

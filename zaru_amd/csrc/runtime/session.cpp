@@ -1566,6 +1566,66 @@ int zr_due_compact_async(const int32_t *d_det_pending, size_t n, const zr_view_d
     });
 }
 
+int zr_due_compact_tiles_async(const int32_t *d_det_pending, size_t n, const zr_view_desc *d_tile_templates,
+                               size_t tiles, int32_t *d_due, int32_t *d_ndue, int32_t *d_due_slots,
+                               zr_view_desc *d_due_views, int32_t *d_nviews, uint64_t *d_total_streams,
+                               uint64_t *d_total_views, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_det_pending || !d_tile_templates || !d_due || !d_ndue || !d_due_slots || !d_due_views || !d_nviews)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "bad stream count");
+        if (tiles < 1 || tiles > 16) return set_err(ZR_ERR_INVALID_ARGUMENT, "tiles must be 1..16");
+        zr::DueTilesParams p{};
+        p.pending = d_det_pending;
+        p.tmpl = reinterpret_cast<const zr::ViewDesc *>(d_tile_templates);
+        p.S = (int)n;
+        p.T = (int)tiles;
+        p.due = d_due;
+        p.ndue = d_ndue;
+        p.due_slots = d_due_slots;
+        p.due_views = reinterpret_cast<zr::ViewDesc *>(d_due_views);
+        p.nviews = d_nviews;
+        p.total_streams = d_total_streams;
+        p.total_views = d_total_views;
+        zr::launch_due_compact_tiles(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_detect_merge_async(const int32_t *d_tile_count, const float *d_tile_dets, const int32_t *d_due,
+                          const int32_t *d_ndue, size_t n, const zr_detmerge_cfg *cfg, int32_t *d_count,
+                          float *d_dets, size_t dcap, int32_t *d_ties, int32_t *d_tile_dropped, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_tile_count || !d_tile_dets || !d_due || !d_ndue || !cfg || !d_count || !d_dets)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "bad stream count");
+        if (cfg->tiles < 1 || cfg->tiles > 16 || cfg->tile_cap < 1 || cfg->tile_cap > 256 ||
+            cfg->tiles * cfg->tile_cap > 1024 || cfg->keypoints < 0 || cfg->keypoints > 7 || dcap == 0 ||
+            dcap > 65536 || cfg->mode < 0 || cfg->mode > 1)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "bad detection merge configuration");
+        zr::DetMergeParams p{};
+        p.tile_count = d_tile_count;
+        p.tile_dets = d_tile_dets;
+        p.due = d_due;
+        p.ndue = d_ndue;
+        p.S = (int)n;
+        p.T = cfg->tiles;
+        p.tile_cap = cfg->tile_cap;
+        p.nkp = cfg->keypoints;
+        p.iou = cfg->iou;
+        p.mode = cfg->mode;
+        p.count = d_count;
+        p.dets = d_dets;
+        p.dcap = (int)dcap;
+        p.ties = d_ties;
+        p.tile_dropped = d_tile_dropped;
+        zr::launch_det_merge(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 int zr_track_lost_compact_async(const zr_track_state *d_state, size_t n, const zr_view_desc *view_template,
                                 int32_t *d_due, int32_t *d_ndue, zr_view_desc *d_due_views, uint64_t *d_total,
                                 void *hip_stream) {

@@ -189,6 +189,35 @@ const char *launch_slot_compact(const SlotCompactParams &p, hipStream_t s);
 // and due_views[k] = the template view with frame = s (one workgroup).
 const char *launch_due_compact(const int32_t *det_pending, const TrackState *lost_of, int S, const ViewDesc &tmpl,
                                int32_t *due, int32_t *ndue, ViewDesc *due_views, uint64_t *total, hipStream_t s);
+// Tiled detection (track.hip): due_compact's scan with T detector views per requesting stream.
+struct DueTilesParams {
+    const int32_t *pending;  // [S]
+    const ViewDesc *tmpl;    // [T] the tiles' views (device; frame set per stream)
+    int S, T;
+    int32_t *due, *ndue;     // [S] / 1: as due_compact
+    int32_t *due_slots;      // [S * T] out: view k * T + t belongs to slot s * T + t
+    ViewDesc *due_views;     // [S * T] out
+    int32_t *nviews;         // out: *ndue * T
+    uint64_t *total_streams, *total_views;  // in / out, may be null
+};
+const char *launch_due_compact_tiles(const DueTilesParams &p, hipStream_t s);
+// Tiled detection (detmerge.hip): the tiles' detections of a stream joined in tile order and put
+// through NonMaxSuppression::process once more.  One wave per due stream.
+struct DetMergeParams {
+    const int32_t *tile_count;  // [S * T] per-tile counts (det_post, mapped; clamped to 0..tile_cap)
+    const float *tile_dets;     // [S * T][tile_cap][20] frame px
+    const int32_t *due, *ndue;  // the streams to merge
+    int S, T, tile_cap, nkp;
+    float iou;
+    int mode;                   // SuppressionMode: 0 Average, 1 Remove
+    int32_t *count;             // [S] out
+    float *dets;                // [S][dcap][20] out
+    int dcap;
+    int32_t *ties;              // [S][2] out, may be null
+    int32_t *tile_dropped;      // [S] out, may be null
+};
+const char *launch_det_merge(const DetMergeParams &p, hipStream_t s);
+size_t det_merge_lds(int tiles, int tile_cap);
 // The face video loop's re-seeding (examples/facemesh.rs:45-54): a stream without RoI takes the
 // bounding rect of its most confident detection (the last of equal maxima) as its RoI.
 struct ReseedParams {

@@ -16,6 +16,12 @@ streams=1, slots=4, device=0)``: K objects per stream with stable ids for any de
 ``set_recognition(model, gallery)`` adds ``"identity"``; with ``gallery.reserve(capacity)`` and
 ``set_enrolment(gallery, first_id, min_embeddings=1)`` unknown faces become gallery rows on the
 device, and ``Gallery.rows()`` reads the enrolled people back.
+
+Tiled detection, for the small faces of a large frame: ``detection_tiles(width, height, cols, rows,
+overlap=0.25, include_full=True)`` gives the rects, ``TiledDetector(network, tiles)`` is the host
+detector over them (``detect``, ``tile_detections``), and
+``DeviceMultiTracker.set_detection_tiles(rects, tile_cap=64)`` runs the same on the device inside
+the loop (``[]`` turns it off).
 """
 from __future__ import annotations
 
