@@ -558,6 +558,8 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
  *     zr_identity_commit_async    write each due object's match and embedding back to it
  *     (with automatic enrolment: zr_embed_match_count_async in place of the match, and
  *      zr_identity_enrol_async here: the unknown objects become gallery rows)
+ *     (with templates: zr_identity_blend_async before the match, which then reads its query rows, as
+ *      the commit does; with refined rows: zr_identity_refine_async between commit and enrolment)
  * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
  * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
  * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
@@ -646,6 +648,54 @@ int zr_identity_enrol_async(const zr_identity_cfg *cfg, size_t n, const int32_t 
                             const float *d_emb_out, float *d_gallery, uint64_t *d_ids, int32_t *d_count,
                             uint64_t *d_next_id, size_t capacity, size_t dim, uint32_t min_embeddings,
                             uint64_t *d_enrolled_total, uint64_t *d_dropped, void *hip_stream);
+/* Identities that learn: two running means, both optional, in one arrangement with the calls above.
+ * One update of a vector m by a sample e with the divisor w (an integer >= 1) is, per float, in f32,
+ * each operation rounded on its own:
+ *     m' = m + (e - m) / (float)w
+ *
+ * The object's template, issued between the embedding network and the match.  For a row i with k =
+ * d_due_of[i] in [0, n), let e be row k of d_dense_emb (this step's network output), t row i of
+ * d_emb_out and c = d_state_out[i].embeddings, both as zr_identity_select_async left them.  Row k of
+ * d_query becomes
+ *     e, bit for bit (-0 and NaN payloads stay), when c == 0 or any of the 128 floats of t or of e is
+ *        not finite: the template starts, or starts again, from a finite embedding;
+ *     t updated by e with w = min(c + 1, template_cap) otherwise (no wrap at c = 0xffffffff): the
+ *        mean of the object's embeddings so far up to template_cap, an exponential average with
+ *        weight 1 / template_cap from there on.
+ * d_dense_emb is only read (zr_identity_refine_async takes the raw samples from it), and rows of
+ * d_query that belong to no due row are not written.  The match and zr_identity_commit_async then
+ * take d_query in place of d_dense_emb, so the object's stored embedding -- and what enrolment
+ * appends -- is the template.  template_cap == 1 is the formula with w = 1, not a copy.
+ * Refused as zr_identity_commit_async refuses cfg, n and NULL pointers, and: template_cap == 0,
+ * d_query == d_dense_emb, d_emb_out, d_dense_emb or d_query not aligned to 8 bytes. */
+int zr_identity_blend_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                            const zr_identity_state *d_state_out, const float *d_emb_out, const float *d_dense_emb,
+                            uint32_t template_cap, float *d_query, void *hip_stream);
+/* Refinement of the gallery rows, issued after zr_identity_commit_async and before
+ * zr_identity_enrol_async.  d_updates holds one count per gallery row (capacity entries): the samples
+ * the row has taken; 0 for a row as it was added, enrolled or reserved.  The rows i = 0 .. n-1 are
+ * taken in row order (stream-major, then slot order).  Row i contributes to gallery row r =
+ * d_state_out[i].row when
+ *     k = d_due_of[i] lies in [0, n)                      (it was embedded this step),
+ *     0 <= r < min(*d_count, capacity),
+ *     d_state_out[i].distance <= update_threshold         (NaN: nobody; +inf: every known object), and
+ *     all 128 floats of row k of d_dense_emb are finite   (the raw sample, not the template).
+ * Each contribution updates row r of d_gallery by that sample with w = min(d_updates[r] + 2,
+ * max_samples), then d_updates[r] = min(d_updates[r] + 1, 0xffffffff): below max_samples the row is the
+ * mean of its first value and its samples, from there on an exponential average with weight 1 /
+ * max_samples.  Contributions to one row are applied one after the other in row order by a single
+ * wavefront, which stores the row once; different rows are independent; no float is added
+ * atomically: the result never depends on scheduling.  States and distances are only read (an
+ * object's distance stays the one measured before this step's refinement), and a row appended by
+ * this step's enrolment is not refined in this step.  *d_refined_total += the contributions applied
+ * (d_refined_total may be NULL).  Nothing eligible: no byte of d_gallery or d_updates is written.
+ * Refused as zr_identity_enrol_async refuses cfg, n, NULL pointers (other than d_refined_total),
+ * capacity, dim and alignment (d_dense_emb 8 bytes, d_gallery 16), and: max_samples < 2. */
+int zr_identity_refine_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                             const zr_identity_state *d_state_out, const float *d_dense_emb, float *d_gallery,
+                             uint32_t *d_updates, const int32_t *d_count, size_t capacity, size_t dim,
+                             uint32_t max_samples, float update_threshold, uint64_t *d_refined_total,
+                             void *hip_stream);
 
 /* ---- Iris and eye-contour refinement of the tracked faces inside the multi-object loop -----
  * The reference has the two halves of the cascade -- FaceMeshV1::left_eye / right_eye

@@ -183,6 +183,8 @@ SIGNATURES = [
     ("zr_identity_compact_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_commit_async", _I, [_P, _SZ, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
     ("zr_identity_enrol_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, _P, _P, _P]),
+    ("zr_identity_blend_async", _I, [_P, _SZ, _P, _P, _P, _P, _U32, _P, _P]),
+    ("zr_identity_refine_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, C.c_float, _P, _P]),
     ("zr_embed_match_count_async", _I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),

@@ -559,6 +559,16 @@ PYBIND11_MODULE(_zaru_host, m) {
         .def("enrolment", &DeviceMultiTracker::enrolment)
         .def("enrolled_total", &DeviceMultiTracker::enrolled_total)
         .def("enrol_dropped", &DeviceMultiTracker::enrol_dropped)
+        // identities that learn: the object's template (1: off), and the refinement of the reserved
+        // gallery set_recognition was given (None turns it off; NaN: the identity threshold)
+        .def("set_identity_smoothing", &DeviceMultiTracker::set_identity_smoothing, py::arg("template_cap"))
+        .def("identity_smoothing", &DeviceMultiTracker::identity_smoothing)
+        .def("set_gallery_refinement", [](DeviceMultiTracker &t, const py::object &gallery, uint32_t max_samples,
+                                          float update_threshold) {
+            t.set_gallery_refinement(gallery.is_none() ? nullptr : gallery.cast<Gallery *>(), max_samples, update_threshold);
+        }, py::arg("gallery"), py::arg("max_samples") = 64, py::arg("update_threshold") = NAN, py::keep_alive<1, 2>())
+        .def("gallery_refinement", &DeviceMultiTracker::gallery_refinement)
+        .def("refined_total", &DeviceMultiTracker::refined_total)
         // iris and eye-contour refinement of every tracked face (FaceMesh V1 / V2)
         .def("set_eye_refinement", &DeviceMultiTracker::set_eye_refinement, py::arg("on"))
         .def("eye_refinement", &DeviceMultiTracker::eye_refinement)
@@ -1108,6 +1118,16 @@ PYBIND11_MODULE(_zaru_host, m) {
             if (!ids.empty()) std::memcpy(a.mutable_data(), ids.data(), ids.size() * sizeof(uint64_t));
             return py::make_tuple(f32_array(r.data(), {(py::ssize_t)ids.size(), (py::ssize_t)g.dim()}), a);
         })
+        // the samples each row in use has taken ([n] u32; DeviceMultiTracker.set_gallery_refinement), and
+        // their restore after add(): a loaded gallery continues its means
+        .def("row_updates", [](Gallery &g) {
+            const std::vector<uint32_t> c = g.row_updates();
+            py::array_t<uint32_t> a((py::ssize_t)c.size());
+            if (!c.empty()) std::memcpy(a.mutable_data(), c.data(), c.size() * sizeof(uint32_t));
+            return a;
+        })
+        .def("set_row_updates", [](Gallery &g, const std::vector<uint32_t> &counts) { g.set_row_updates(counts); },
+             py::arg("counts"))
         .def("add", [](Gallery &g, py::array_t<float, py::array::c_style> rows, const std::vector<uint64_t> &ids) {
             if ((size_t)rows.size() != ids.size() * g.dim()) throw ZaruError(ZR_ERR_SHAPE, "rows must be [len(ids)][dim]");
             g.add(rows.data(), ids.data(), ids.size());

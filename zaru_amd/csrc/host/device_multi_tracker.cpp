@@ -122,7 +122,7 @@ DeviceMultiTracker::~DeviceMultiTracker() {
     }
     if (snap_.copy_stream) (void)zr_stream_destroy(snap_.copy_stream);  // idle: objects_packed waits for its copies
     if (snap_.event) (void)zr_event_destroy(snap_.event);
-    if (enrol_) enrol_->end_enrol(this);  // (the gallery outlives the tracker: set_recognition)
+    if (written()) written()->end_enrol(this);  // (the gallery outlives the tracker: set_recognition)
 }
 
 void DeviceMultiTracker::set_redetect_interval(double ms) {
@@ -221,7 +221,8 @@ void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, cons
     snap_.pending = false;  // a snapshot's identities name rows of the gallery it was taken with
     if (model.empty() || !gallery) {
         synchronize();  // the last step's launches still read the network and the gallery
-        enrol_ = nullptr;
+        enrol_ = refine_ = nullptr;
+        template_cap_ = 1;
         embedder_.reset();
         gallery_ = nullptr;
         id_ran_ = false;
@@ -231,6 +232,8 @@ void DeviceMultiTracker::set_recognition(const std::vector<uint8_t> &model, cons
     auto emb = std::make_unique<FaceEmbedder>(model, device_);  // throws before anything changes
     synchronize();
     enrol_ = nullptr;  // enrolment belongs to the gallery it was set for: set_enrolment again
+    refine_ = nullptr;  // and so do refinement and smoothing
+    template_cap_ = 1;
     embedder_ = std::move(emb);
     gallery_ = gallery;
     const AspectRatio a = embedder_->cnn().aspect();
@@ -294,6 +297,35 @@ void DeviceMultiTracker::set_enrolment(Gallery *gallery, uint64_t first_id, uint
     enrol_min_ = min_embeddings;
 }
 
+void DeviceMultiTracker::set_identity_smoothing(uint32_t template_cap) {
+    if (template_cap < 1) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "template_cap must be >= 1");
+    if (!embedder_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "identity smoothing needs recognition (set_recognition)");
+    template_cap_ = template_cap;  // read when the next step is enqueued; the objects keep what they have
+}
+
+void DeviceMultiTracker::set_gallery_refinement(Gallery *gallery, uint32_t max_samples, float update_threshold) {
+    if (!gallery) {
+        synchronize();
+        refine_ = nullptr;
+        return;
+    }
+    if (!embedder_ || gallery != gallery_)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "refinement needs the gallery set_recognition was given");
+    if (!gallery->reserved()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "refinement needs a reserved gallery (Gallery::reserve)");
+    if (max_samples < 2) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "max_samples must be >= 2");
+    synchronize();
+    gallery->begin_enrol(this);  // throws while another tracker's writing steps may be in flight
+    gallery->end_enrol(this);
+    if (!refine_total_.ptr) {
+        refine_total_.resize(1);
+        check(zr_memset_async(refine_total_.ptr, 0, 8, stream_));
+        check(zr_stream_synchronize(stream_));
+    }
+    refine_ = gallery;
+    refine_max_ = max_samples;
+    refine_threshold_ = update_threshold;
+}
+
 // a valid view in every entry of the packed crop table, as frame_size() does for the other two
 void DeviceMultiTracker::reset_identity_views() {
     const size_t K = (size_t)cfg_.slots, nv = n_ * K;
@@ -318,17 +350,31 @@ void DeviceMultiTracker::identify(const std::vector<zr_frame> &zf, double now_ms
     float *eouts[1] = {id_dense_emb_.ptr};
     check(zr_cnn_estimate_device_views_count_async(ec.nn().handle(), zf.data(), n_, id_due_views_.ptr, nv,
                                                    id_ndue_.ptr, cm.lo, cm.hi, eouts, stream_));
+    // with smoothing the match and the commit read the templates; the raw samples stay for the refinement
+    const float *query = id_dense_emb_.ptr;
+    if (template_cap_ > 1) {
+        id_query_.resize(nv * EMBEDDING_DIM);
+        check(zr_identity_blend_async(&icfg_, nv, id_due_of_.ptr, id_state_[out].ptr, id_emb_[out].ptr,
+                                      id_dense_emb_.ptr, template_cap_, id_query_.ptr, stream_));
+        query = id_query_.ptr;
+    }
     if (enrol_) {
         // the gallery's size is the device's: the previous step may have appended to it
-        check(zr_embed_match_count_async(id_dense_emb_.ptr, nv, enrol_->device_rows_mut(), enrol_->capacity(),
+        check(zr_embed_match_count_async(query, nv, enrol_->device_rows_mut(), enrol_->capacity(),
                                          enrol_->device_count(), EMBEDDING_DIM, id_valid_.ptr, id_best_idx_.ptr,
                                          id_best_dist_.ptr, stream_));
     } else {
-        check(zr_embed_match_async(id_dense_emb_.ptr, nv, gallery_->device_rows(), gallery_->size(), EMBEDDING_DIM,
+        check(zr_embed_match_async(query, nv, gallery_->device_rows(), gallery_->size(), EMBEDDING_DIM,
                                    id_valid_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, nullptr, stream_));
     }
-    check(zr_identity_commit_async(&icfg_, nv, id_due_of_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, id_dense_emb_.ptr,
-                                   now_ms, id_state_[out].ptr, id_emb_[out].ptr, stream_));
+    check(zr_identity_commit_async(&icfg_, nv, id_due_of_.ptr, id_best_idx_.ptr, id_best_dist_.ptr, query, now_ms,
+                                   id_state_[out].ptr, id_emb_[out].ptr, stream_));
+    if (refine_)
+        check(zr_identity_refine_async(&icfg_, nv, id_due_of_.ptr, id_state_[out].ptr, id_dense_emb_.ptr,
+                                       refine_->device_rows_mut(), refine_->device_updates(), refine_->device_count(),
+                                       refine_->capacity(), EMBEDDING_DIM, refine_max_,
+                                       std::isnan(refine_threshold_) ? icfg_.threshold : refine_threshold_,
+                                       refine_total_.ptr, stream_));
     if (enrol_)
         check(zr_identity_enrol_async(&icfg_, nv, id_due_of_.ptr, id_state_[out].ptr, id_emb_[out].ptr,
                                       enrol_->device_rows_mut(), enrol_->device_ids(), enrol_->device_count(),
@@ -507,7 +553,7 @@ void DeviceMultiTracker::apply_injected() {
 void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
     if (embedder_ && std::isnan(now_ms)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "recognition needs a frame clock");
-    if (enrol_) enrol_->begin_enrol(this);  // refused while another tracker's enrolling steps may be in flight
+    if (written()) written()->begin_enrol(this);  // refused while another tracker's writing steps may be in flight
     // both checked before anything is enqueued: this frame's elapsed, and the previous frame's that
     // this step filters with
     float el = 0.f;
@@ -603,7 +649,7 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
 
 void DeviceMultiTracker::synchronize() {
     if (stream_) check(zr_stream_synchronize(stream_));
-    if (enrol_) enrol_->end_enrol(this);
+    if (written()) written()->end_enrol(this);
 }
 
 std::vector<int32_t> DeviceMultiTracker::read_i32(const DeviceArray<int32_t> &a) {
@@ -651,6 +697,7 @@ uint64_t DeviceMultiTracker::enrol_dropped() {
     synchronize();
     return v;
 }
+uint64_t DeviceMultiTracker::refined_total() { return refine_total_.ptr ? read_u64(refine_total_) : 0; }
 uint64_t DeviceMultiTracker::eye_images() { return eye_total_.ptr ? read_u64(eye_total_) : 0; }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {

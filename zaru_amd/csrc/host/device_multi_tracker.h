@@ -40,7 +40,11 @@
 //   d. zr_embed_match_async against the gallery's rows as they are at this step,
 //   e. zr_identity_commit_async: match, distance, count, next time and embedding written back,
 //   f. with set_enrolment: d. is zr_embed_match_count_async (the gallery's size read on the device),
-//      and zr_identity_enrol_async appends the unknown objects to the gallery (kernels/enrol.hip).
+//      and zr_identity_enrol_async appends the unknown objects to the gallery (kernels/enrol.hip),
+//   g. with set_identity_smoothing: zr_identity_blend_async between c. and d. (the object's
+//      template: its stored embedding moved towards this step's), and d. and e. read the blended rows,
+//   h. with set_gallery_refinement: zr_identity_refine_async between e. and f. (each known object's
+//      gallery row moved towards its raw sample of this step; kernels/template.hip).
 // The crop is taken from this step's frame at the place the previous frame's landmarks give: the
 // one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
 // frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
@@ -63,6 +67,7 @@
 // give: recognition's one frame of lag.  With a filter set the rects come from the filtered landmarks.
 // The eye landmarks themselves are not filtered.
 #pragma once
+#include <cmath>
 #include <memory>
 #include <optional>
 #include <vector>
@@ -149,6 +154,25 @@ class DeviceMultiTracker {
     bool enrolment() const { return enrol_ != nullptr; }
     uint64_t enrolled_total();  // rows this tracker's steps appended, summed (0 before set_enrolment)
     uint64_t enrol_dropped();   // candidates that found the gallery full, summed
+    // Identities that learn (zr_identity_blend_async / zr_identity_refine_async in include/zaru_hip.h
+    // have the rules; both are settings, chosen and not tuned).
+    // Smoothing: an object's embedding becomes the running mean of its embeddings -- of all of them
+    // up to `template_cap`, an exponential average with weight 1 / template_cap from there on -- and
+    // that template is what is matched, stored, reported, exported and enrolled.  min_embeddings then
+    // means "enrol the mean of at least that many looks".  1 turns it off; needs recognition; resets
+    // no object; every set_recognition turns it off.
+    void set_identity_smoothing(uint32_t template_cap);
+    uint32_t identity_smoothing() const { return template_cap_; }
+    // Refinement: at every embedding of an object that is known within `update_threshold` (NaN: the
+    // identity threshold as it is at each step), its gallery row takes the raw embedding as one more
+    // sample of its mean, up to `max_samples` (an exponential average from there on).  Same-step
+    // contributors to one row are applied in row order (stream-major, then slot order).  `gallery`
+    // must be the gallery set_recognition was given, and reserved; nullptr turns refinement off, as
+    // does every call of set_recognition.  The tracker is a writer of the gallery, under the one-writer
+    // rule of set_enrolment.  Read the rows with Gallery::rows(), their counts with row_updates().
+    void set_gallery_refinement(Gallery *gallery, uint32_t max_samples = 64, float update_threshold = NAN);
+    bool gallery_refinement() const { return refine_ != nullptr; }
+    uint64_t refined_total();   // contributions this tracker's steps applied, summed
     // Eye refinement of every tracked face, every step (default off).  Refused unless the
     // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
     // step enqueues what it did without, and objects() reports no eyes.
@@ -297,6 +321,13 @@ class DeviceMultiTracker {
     Gallery *enrol_ = nullptr;           // gallery_, when enrolment is on
     uint32_t enrol_min_ = 1;
     DeviceArray<uint64_t> enrol_counts_;  // [0] rows appended, [1] candidates dropped
+    uint32_t template_cap_ = 1;          // > 1: smoothing is on
+    DeviceArray<float> id_query_;        // the blended rows, sized like id_dense_emb_ at the first step that needs it
+    Gallery *refine_ = nullptr;          // gallery_, when refinement is on
+    uint32_t refine_max_ = 64;
+    float refine_threshold_ = NAN;       // NaN: the identity threshold at each step
+    DeviceArray<uint64_t> refine_total_; // [0] contributions applied
+    Gallery *written() const { return enrol_ ? enrol_ : refine_; }  // the gallery this tracker's steps write
     // eye refinement: 2 entries per slot (left, right), the packed batch and the atlas it is cropped into
     std::shared_ptr<const Cnn> eye_cnn_;
     zr_eye_cfg ecfg_{};

@@ -135,6 +135,8 @@ void Gallery::reserve(size_t capacity) {
     count_.resize(1);
     next_id_.resize(1);
     dev_ids_.resize(capacity);
+    updates_.resize(capacity);
+    check(zr_memset_async(updates_.ptr, 0, capacity * sizeof(uint32_t), stream_));
     const int32_t count = (int32_t)have;
     check(zr_memset_async(dev_ids_.ptr, 0, capacity * sizeof(uint64_t), stream_));
     if (have) check(zr_memcpy_async(dev_ids_.ptr, ids_.data(), have * sizeof(uint64_t), 0, stream_));
@@ -150,8 +152,28 @@ void Gallery::clear() {
     if (!reserved_) return;
     check(zr_memset_async(count_.ptr, 0, sizeof(int32_t), stream_));
     check(zr_memset_async(next_id_.ptr, 0, sizeof(uint64_t), stream_));
+    check(zr_memset_async(updates_.ptr, 0, cap_ * sizeof(uint32_t), stream_));
     check(zr_stream_synchronize(stream_));
     enrolled_ = 0;
+}
+
+std::vector<uint32_t> Gallery::row_updates() {
+    if (!reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is not reserved");
+    refresh();
+    std::vector<uint32_t> counts(ids_.size());
+    if (counts.empty()) return counts;
+    check(zr_memcpy_async(counts.data(), updates_.ptr, counts.size() * sizeof(uint32_t), 1, stream_));
+    check(zr_stream_synchronize(stream_));
+    return counts;
+}
+
+void Gallery::set_row_updates(const std::vector<uint32_t> &counts) {
+    if (!reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is not reserved");
+    refresh();
+    if (counts.size() != ids_.size()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one update count per row in use");
+    if (counts.empty()) return;
+    check(zr_memcpy_async(updates_.ptr, counts.data(), counts.size() * sizeof(uint32_t), 0, stream_));
+    check(zr_stream_synchronize(stream_));
 }
 
 void Gallery::refresh() {

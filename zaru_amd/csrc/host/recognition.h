@@ -95,8 +95,19 @@ class Gallery {
     uint64_t *device_next_id() { return next_id_.ptr; }
     // the next person id becomes `first_id` if the device has enrolled nobody yet (refreshes)
     void seed_next_id(uint64_t first_id);
-    // One enrolling tracker at a time: a tracker announces the steps it enqueues (begin) and that it
-    // has synchronised (end).  begin throws while another owner's steps may still be in flight.
+    // Refined rows (DeviceMultiTracker::set_gallery_refinement): a reserved gallery keeps, on the
+    // device, how many samples each row has taken (zr_identity_refine_async's d_updates): 0 for a
+    // row as add(), enrolment or reserve() made it, and after clear().  row_updates() refreshes and
+    // returns the counts of the rows in use; set_row_updates() takes one count per row in use, so
+    // that a gallery saved with rows() + row_updates() and loaded with add() + set_row_updates()
+    // continues its means instead of starting them again.  Both throw for an unreserved gallery;
+    // call them, like add(), after the writing tracker's synchronize().
+    uint32_t *device_updates() { return updates_.ptr; }
+    std::vector<uint32_t> row_updates();
+    void set_row_updates(const std::vector<uint32_t> &counts);
+    // One writing tracker (enrolling or refining) at a time: a tracker announces the steps it enqueues
+    // (begin) and that it has synchronised (end).  begin throws while another owner's steps may
+    // still be in flight.
     void begin_enrol(const void *owner);
     void end_enrol(const void *owner);
 
@@ -111,6 +122,7 @@ class Gallery {
     const void *enroller_ = nullptr;  // the tracker whose enqueued steps may append (nullptr: none in flight)
     DeviceArray<int32_t> count_;
     DeviceArray<uint64_t> dev_ids_, next_id_;
+    DeviceArray<uint32_t> updates_;  // [cap_] samples taken per row (reserved galleries only)
 };
 
 struct Recognition {

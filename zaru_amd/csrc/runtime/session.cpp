@@ -1320,6 +1320,65 @@ int zr_identity_enrol_async(const zr_identity_cfg *cfg, size_t n, const int32_t 
     });
 }
 
+// ---- templates and refined gallery rows (kernels/template.hip)
+int zr_identity_blend_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                            const zr_identity_state *d_state_out, const float *d_emb_out, const float *d_dense_emb,
+                            uint32_t template_cap, float *d_query, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_state_out || !d_emb_out || !d_dense_emb || !d_query)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_identity(cfg, n, 0.0)) return rc;
+        if (template_cap < 1) return set_err(ZR_ERR_INVALID_ARGUMENT, "template_cap must be >= 1");
+        if (d_query == d_dense_emb)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the query must be a buffer of its own: the raw samples stay");
+        if ((uintptr_t)d_emb_out % 8 || (uintptr_t)d_dense_emb % 8 || (uintptr_t)d_query % 8)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "embedding buffers must be aligned to 8 bytes");
+        zr::IdentityBlendParams p{};
+        p.due_of = d_due_of;
+        p.out = reinterpret_cast<const zr::IdentityState *>(d_state_out);
+        p.emb_out = d_emb_out;
+        p.dense_emb = d_dense_emb;
+        p.query = d_query;
+        p.n = (int)n;
+        p.template_cap = template_cap;
+        zr::launch_identity_blend(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+int zr_identity_refine_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
+                             const zr_identity_state *d_state_out, const float *d_dense_emb, float *d_gallery,
+                             uint32_t *d_updates, const int32_t *d_count, size_t capacity, size_t dim,
+                             uint32_t max_samples, float update_threshold, uint64_t *d_refined_total,
+                             void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_state_out || !d_dense_emb || !d_gallery || !d_updates || !d_count)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (int rc = check_identity(cfg, n, 0.0)) return rc;
+        if (capacity < 1 || capacity > 0x7fffffffu) return set_err(ZR_ERR_INVALID_ARGUMENT, "capacity must be 1..2^31-1");
+        if (dim != (size_t)zr::IDENTITY_DIM) return set_err(ZR_ERR_INVALID_ARGUMENT, "refinement needs 128-float rows");
+        if (max_samples < 2) return set_err(ZR_ERR_INVALID_ARGUMENT, "max_samples must be >= 2");
+        if ((uintptr_t)d_dense_emb % 8 || (uintptr_t)d_gallery % 16)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "embeddings must be aligned to 8 bytes, gallery rows to 16");
+        zr::IdentityRefineParams p{};
+        p.due_of = d_due_of;
+        p.out = reinterpret_cast<const zr::IdentityState *>(d_state_out);
+        p.dense_emb = d_dense_emb;
+        p.rows = d_gallery;
+        p.updates = d_updates;
+        p.count = d_count;
+        p.refined_total = d_refined_total;
+        p.n = (int)n;
+        p.capacity = (int)capacity;
+        p.max_samples = max_samples;
+        p.threshold = update_threshold;
+        zr::launch_identity_refine(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 // ---- eye refinement of the tracked faces (kernels/eye.hip)
 static int check_eye(const zr_eye_cfg *cfg, size_t n) {
     if (!cfg) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");

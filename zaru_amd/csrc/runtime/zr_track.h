@@ -300,6 +300,32 @@ struct IdentityEnrolParams {
     float threshold;
 };
 const char *launch_identity_enrol(const IdentityEnrolParams &p, hipStream_t s);
+// The object's template (kernels/template.hip), between the embedding network and the match: for a
+// due row i with k = due_of[i], query[k] = dense_emb[k] moved into the embedding select carried.
+struct IdentityBlendParams {
+    const int32_t *due_of;    // [n]
+    const IdentityState *out; // [n] select's output: embeddings is the count before this step's commit
+    const float *emb_out;     // [n][IDENTITY_DIM] select's output: the stored embedding
+    const float *dense_emb;   // [n][IDENTITY_DIM] by packed image: the network's output, only read
+    float *query;             // [n][IDENTITY_DIM] by packed image, out; rows of no due object are not written
+    int n;
+    uint32_t template_cap;    // >= 1
+};
+const char *launch_identity_blend(const IdentityBlendParams &p, hipStream_t s);
+// Refinement of the gallery rows (kernels/template.hip), after the commit and before the enrolment.
+struct IdentityRefineParams {
+    const int32_t *due_of;    // [n]
+    const IdentityState *out; // [n] the committed states
+    const float *dense_emb;   // [n][IDENTITY_DIM] by packed image: the raw samples
+    float *rows;              // [capacity][IDENTITY_DIM] the gallery, in / out
+    uint32_t *updates;        // [capacity] in / out: samples a row has taken
+    const int32_t *count;     // rows in the gallery
+    uint64_t *refined_total;  // in / out: += contributions applied; may be null
+    int n, capacity;
+    uint32_t max_samples;     // >= 2
+    float threshold;
+};
+const char *launch_identity_refine(const IdentityRefineParams &p, hipStream_t s);
 
 // Eye refinement of the tracked faces (kernels/eye.hip): entry 2i is row i's left eye, 2i + 1 its
 // right eye.  The packing between select and crop is identity_compact_kernel over the 2n entries.

@@ -15,7 +15,12 @@ streams=1, slots=4, device=0)``: K objects per stream with stable ids for any de
 ``set_pose_reference``) for stream ``s``, ``object_counts()`` every stream's objects.
 ``set_recognition(model, gallery)`` adds ``"identity"``; with ``gallery.reserve(capacity)`` and
 ``set_enrolment(gallery, first_id, min_embeddings=1)`` unknown faces become gallery rows on the
-device, and ``Gallery.rows()`` reads the enrolled people back.
+device, and ``Gallery.rows()`` reads the enrolled people back.  Identities that learn:
+``set_identity_smoothing(template_cap)`` makes an object's embedding the running mean of its
+embeddings (what is matched, reported and enrolled), and ``set_gallery_refinement(gallery,
+max_samples=64, update_threshold=nan)`` moves a known object's gallery row towards each new embedding
+of it, on the device; ``refined_total()`` counts, ``Gallery.row_updates()`` / ``set_row_updates(counts)``
+save and restore the rows' sample counts beside ``rows()`` / ``add()``.
 
 Tiled detection, for the small faces of a large frame: ``detection_tiles(width, height, cols, rows,
 overlap=0.25, include_full=True)`` gives the rects, ``TiledDetector(network, tiles)`` is the host
