@@ -1,8 +1,6 @@
 // device_hand_tracker.cpp -- see device_hand_tracker.h.
 #include "device_hand_tracker.h"
 
-#include <algorithm>
-
 #include "device_tracker.h"
 #include "hand_tracker.h"
 
@@ -134,45 +132,7 @@ void DeviceHandTracker::step(const std::vector<Image> &frames, double now_ms) {
         check(zr_stream_synchronize(stream_));
     }
     // injected detections replace the palm result this step consumes (test hook)
-    bool any = false;
-    for (auto &v : injected_) any = any || !v.empty();
-    if (any) {
-        check(zr_stream_synchronize(stream_));
-        std::vector<int32_t> cnt(n_), pend(n_);
-        std::vector<float> d(n_ * dcap_ * 20, 0.f);
-        check(zr_memcpy_async(cnt.data(), count_.ptr, n_ * 4, 1, stream_));
-        check(zr_memcpy_async(pend.data(), det_pending_.ptr, n_ * 4, 1, stream_));
-        check(zr_memcpy_async(d.data(), dets_.ptr, d.size() * 4, 1, stream_));
-        check(zr_stream_synchronize(stream_));
-        for (size_t s = 0; s < n_; s++) {
-            if (injected_[s].empty()) continue;
-            // the host tracker's order: the injected detections, then the finished palm result
-            std::vector<float> palm;
-            const int np = pend[s] ? std::min(cnt[s], (int32_t)dcap_) : 0;
-            palm.assign(d.begin() + s * dcap_ * 20, d.begin() + (s * dcap_ + np) * 20);
-            cnt[s] = 0;
-            pend[s] = 1;
-            for (const Detection &det : injected_[s]) {
-                if ((size_t)cnt[s] >= dcap_) break;
-                float *r = d.data() + (s * dcap_ + cnt[s]) * 20;
-                std::fill(r, r + 20, 0.f);
-                r[0] = det.confidence;
-                r[1] = det.angle;
-                r[2] = det.rect.center().x;
-                r[3] = det.rect.center().y;
-                r[4] = det.rect.width();
-                r[5] = det.rect.height();
-                cnt[s]++;
-            }
-            for (int k = 0; k < np && (size_t)cnt[s] < dcap_; k++, cnt[s]++)
-                std::copy(palm.begin() + k * 20, palm.begin() + (k + 1) * 20, d.begin() + (s * dcap_ + cnt[s]) * 20);
-            injected_[s].clear();
-        }
-        check(zr_memcpy_async(count_.ptr, cnt.data(), n_ * 4, 0, stream_));
-        check(zr_memcpy_async(det_pending_.ptr, pend.data(), n_ * 4, 0, stream_));
-        check(zr_memcpy_async(dets_.ptr, d.data(), d.size() * 4, 0, stream_));
-        check(zr_stream_synchronize(stream_));
-    }
+    apply_injected_detections(stream_, n_, dcap_, count_.ptr, det_pending_.ptr, dets_.ptr, injected_);
     const size_t nv = n_ * (size_t)cfg_.slots;
     const NeuralNetwork &hn = hand_->nn();
     // 1. the previous step's estimates (tracking.rs:116-127: the workers' results)

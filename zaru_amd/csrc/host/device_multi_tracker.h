@@ -18,65 +18,21 @@
 //   5. the landmark network on exactly those views (zr_cnn_estimate_device_views_count_async),
 //   6. the detector on the streams step 3 asked to detect on, as DeviceHandTracker runs BlazePalm
 //      (zr_due_compact_async, the counted launches, zr_detect_post_mapped_async).
-//      With detection tiles set (set_detection_tiles; host/detection.h has the semantics) step 6 is
-//      zr_due_compact_tiles_async (T views per due stream), the counted launches on streams x T
-//      views, zr_detect_post_mapped_async over streams x T rows with one letterbox row per tile and
-//      tile_cap records each, and zr_detect_merge_async into the same count / list: steps 1-5 and
-//      everything that reads the detections see no difference.
+//      With detection tiles set (set_detection_tiles) step 6 is MultiTiles::enqueue instead.
 // Schedule: a detection requested at step t is taken at step t + 1 (DeviceHandTracker's).
 // Face detectors start an object on the detection's bounding rect, unrotated and with the
 // LandmarkTracker's default padding (examples/facemesh.rs:49-54); the palm detector with
 // HandTracker's grow factor, angle and padding, which makes ("palm", "hand") DeviceHandTracker.
 //
-// Recognition (opt-in, set_recognition): every object carries an identity -- the gallery row it
-// matched, the distance, how often it was embedded, its last embedding and when it is due again --
-// that follows it between slots through step 3's `src`, as the filter state does.  Between steps 2
-// and 3 a step enqueues
-//   a. zr_identity_select_async: each object's identity gathered from the slot it held, the
-//      schedule (never embedded, or now_ms reached its next time), and for a due object the crop
-//      around its landmarks (landmark_crop_view, recognition.h),
-//   b. zr_identity_compact_async: the due crops packed, with a device count,
-//   c. the embedding network on exactly those (zr_cnn_estimate_device_views_count_async),
-//   d. zr_embed_match_async against the gallery's rows as they are at this step,
-//   e. zr_identity_commit_async: match, distance, count, next time and embedding written back,
-//   f. with set_enrolment: d. is zr_embed_match_count_async (the gallery's size read on the device),
-//      and zr_identity_enrol_async appends the unknown objects to the gallery (kernels/enrol.hip),
-//   g. with set_identity_smoothing: zr_identity_blend_async between c. and d. (the object's
-//      template: its stored embedding moved towards this step's), and d. and e. read the blended rows,
-//   h. with set_gallery_refinement: zr_identity_refine_async between e. and f. (each known object's
-//      gallery row moved towards its raw sample of this step; kernels/template.hip).
-// The crop is taken from this step's frame at the place the previous frame's landmarks give: the
-// one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
-// frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
-// landmarks.  A new object is identified at the first step it has a result.
-//
-// Eye refinement (opt-in, set_eye_refinement; FaceMesh V1 / V2): the iris and eye-contour points of
-// both eyes of every tracked face (host/eye.h: the reference's left_eye / right_eye rects joined to
-// its EyeNetwork).  After step 2 -- and after recognition's calls -- and before step 3 a step enqueues,
-// for every tracked row, every step,
-//   a. zr_eye_select_async: per eye (entry 2i left, 2i + 1 right) validity, crop and sampling view,
-//   b. zr_identity_compact_async over the 2n entries: the valid eyes packed, with a device count,
-//   c. zr_eye_crop_async: each packed eye as a 64 x 64 RGBA cell of an atlas, a right eye mirrored,
-//   d. the eye network on the atlas's first `count` cells (zr_cnn_estimate_device_views_count_async
-//      with a constant table of identity cell views),
-//   e. zr_eye_commit_async: extract, un-mirror, map to frame px, iris diameter, per entry.
-// The atlas (16 KB written and read per eye) is a decision: a mirror flag in the sampler would touch
-// every stem kernel on the benchmarked path.  The results are per slot, written before step 3 moves
-// the objects, and paired with them through `src` in objects(), as the pose and the identity are.
-// The crop is taken from this step's frame at the place the reported (previous-frame) landmarks
-// give: recognition's one frame of lag.  With a filter set the rects come from the filtered landmarks.
-// The eye landmarks themselves are not filtered.
+// The optional stages -- recognition with enrolment and templates, eye refinement, detection tiles
+// and the packed export -- are structs of their own with their protocols beside them: multi_stages.h.
 #pragma once
 #include <cmath>
 #include <memory>
 #include <optional>
 #include <vector>
 
-#include "detection.h"
-#include "device_tracker.h"
-#include "eye.h"
-#include "landmark.h"
-#include "recognition.h"
+#include "multi_stages.h"
 
 namespace zh {
 
@@ -107,7 +63,7 @@ class DeviceMultiTracker {
     // zr_detect_merge_async refuses: more than 16 rects, tile_cap outside 1..256, rects x tile_cap
     // above 1024.
     void set_detection_tiles(const std::vector<Rect> &rects, uint32_t tile_cap = DEFAULT_TILE_CAP);
-    const std::vector<Rect> &detection_tiles() const { return tiles_; }
+    const std::vector<Rect> &detection_tiles() const { return tiles_.rects; }
     // head pose of every object against `points` (n x 3 floats, e.g. the canonical face mesh; empty:
     // off, the default), as DeviceFaceLoop::set_pose_reference
     void set_pose_reference(const std::vector<float> &points, bool flip_y = true);
@@ -127,13 +83,13 @@ class DeviceMultiTracker {
     // model or a null gallery turns recognition off: a step then enqueues what it did without.
     // Every call resets every object's identity: each live object is embedded at the next step.
     void set_recognition(const std::vector<uint8_t> &model, const Gallery *gallery);
-    bool recognition() const { return embedder_ != nullptr; }
+    bool recognition() const { return identity_.on(); }
     // an object is embedded again once `ms` passed since its last embedding (default 1000; 0:
     // every step; +inf: once per object).  Applies from each object's next embedding on.
     void set_identify_interval(double ms);
     // a match counts as known when distance <= d (default +inf: the nearest row always, as
     // Gallery::match; NaN: never).  Applies to the embeddings made from now on.
-    void set_identity_threshold(float d) { icfg_.threshold = d; }
+    void set_identity_threshold(float d) { identity_.cfg.threshold = d; }
     // grow_rel factor of the landmarks' bounding rect (default FaceEmbedder::CROP_GROW)
     void set_identity_crop_grow(float g);
     // Automatic enrolment: an object that matches no row (after `min_embeddings` embeddings, never
@@ -151,7 +107,7 @@ class DeviceMultiTracker {
     // enrol into it once this one has synchronised, and its step() throws where that can be seen
     // (this tracker has stepped since its last synchronize()).
     void set_enrolment(Gallery *gallery, uint64_t first_id, uint32_t min_embeddings = 1);
-    bool enrolment() const { return enrol_ != nullptr; }
+    bool enrolment() const { return identity_.enrol != nullptr; }
     uint64_t enrolled_total();  // rows this tracker's steps appended, summed (0 before set_enrolment)
     uint64_t enrol_dropped();   // candidates that found the gallery full, summed
     // Identities that learn (zr_identity_blend_async / zr_identity_refine_async in include/zaru_hip.h
@@ -162,7 +118,7 @@ class DeviceMultiTracker {
     // means "enrol the mean of at least that many looks".  1 turns it off; needs recognition; resets
     // no object; every set_recognition turns it off.
     void set_identity_smoothing(uint32_t template_cap);
-    uint32_t identity_smoothing() const { return template_cap_; }
+    uint32_t identity_smoothing() const { return identity_.template_cap; }
     // Refinement: at every embedding of an object that is known within `update_threshold` (NaN: the
     // identity threshold as it is at each step), its gallery row takes the raw embedding as one more
     // sample of its mean, up to `max_samples` (an exponential average from there on).  Same-step
@@ -171,13 +127,13 @@ class DeviceMultiTracker {
     // does every call of set_recognition.  The tracker is a writer of the gallery, under the one-writer
     // rule of set_enrolment.  Read the rows with Gallery::rows(), their counts with row_updates().
     void set_gallery_refinement(Gallery *gallery, uint32_t max_samples = 64, float update_threshold = NAN);
-    bool gallery_refinement() const { return refine_ != nullptr; }
+    bool gallery_refinement() const { return identity_.refine != nullptr; }
     uint64_t refined_total();   // contributions this tracker's steps applied, summed
     // Eye refinement of every tracked face, every step (default off).  Refused unless the
     // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
     // step enqueues what it did without, and objects() reports no eyes.
     void set_eye_refinement(bool on);
-    bool eye_refinement() const { return eye_on_; }
+    bool eye_refinement() const { return eyes_.on(); }
     // grow_rel factor of the eye rect (default EYE_CROP_GROW, 0.65)
     void set_eye_crop_grow(float g);
     // one device-resident frame per stream (all of one size); `now_ms` stands for Instant::now().
@@ -225,22 +181,7 @@ class DeviceMultiTracker {
     // as do set_recognition and set_enrolment (they drop it).  Nothing of this runs, and nothing is
     // allocated, unless snapshot() or objects_packed() is called.
     void snapshot();
-    struct PackedObjects {
-        size_t count = 0;                           // objects with a result, over all streams
-        size_t num_landmarks = 0;                   // L
-        const int32_t *stream_offsets = nullptr;    // [streams + 1]: stream s owns records [off[s], off[s + 1])
-        const zr_export_header *headers = nullptr;  // [count] stream, slot, id, roi, confidence, flags
-        const float *landmarks = nullptr;           // [count][L][3]
-        // absent (nullptr) exactly where objects() leaves the field out
-        const zr_pose *pose = nullptr;                  // [count]
-        const zr_export_identity *identity = nullptr;   // [count]; flags & ZR_EXPORT_IDENTITY: embedded yet
-        const uint64_t *identity_id = nullptr;          // [count] Identity::id (NO_MATCH: unknown or none)
-        const float *embedding = nullptr;               // [count][128]
-        const int32_t *eye_valid = nullptr;             // [count][2] left, right
-        const float *iris_diameter = nullptr;           // [count][2]
-        const float *eye_crop = nullptr;                // [count][2][5]
-        const float *eye_landmarks = nullptr;           // [count][2][76][3]
-    };
+    using PackedObjects = MultiPackedObjects;  // count, stream_offsets and the arrays (multi_stages.h)
     // The pending snapshot's records, or -- none pending -- those of a snapshot taken now: waits for the
     // snapshot's event only (not for steps enqueued since), then copies exactly `count` rows of each
     // present array to page-locked staging on a stream of its own, with one wait: at most nine
@@ -262,13 +203,11 @@ class DeviceMultiTracker {
 
   private:
     void frame_size(uint32_t W, uint32_t H);
-    void apply_injected();
-    void reset_tile_views();
-    void identify(const std::vector<zr_frame> &zf, double now_ms);
-    void reset_identity_views();
-    void refine_eyes(const std::vector<zr_frame> &zf);
+    MultiCtx ctx() const;           // what the stages are handed of the loop
+    MultiDetector detector_leg();   // and MultiTiles of its detector
+    // a per-stream array, and element `at` of a counter; zeros while it was never allocated
     std::vector<int32_t> read_i32(const DeviceArray<int32_t> &a);
-    uint64_t read_u64(const DeviceArray<uint64_t> &a);
+    uint64_t read_u64(const DeviceArray<uint64_t> &a, size_t at = 0);
     std::shared_ptr<const Cnn> det_, lm_;
     DetectorNetwork det_net_;
     LandmarkNetwork lm_net_;
@@ -293,68 +232,17 @@ class DeviceMultiTracker {
     DeviceArray<int32_t> due_, ndue_;
     zr_view_desc det_tmpl_{};  // the letterboxed detector view (frame index set per stream)
     DeviceArray<uint64_t> due_total_, lm_total_;
-    // tiled detection: the tiles' template views, the packed views x T table with its slot map and
-    // count, the per-tile letterbox rows, and the per-tile lists the merge reads
-    std::vector<Rect> tiles_;
-    uint32_t tile_cap_ = DEFAULT_TILE_CAP;
-    DeviceArray<zr_view_desc> tile_tmpl_, tile_views_;
-    DeviceArray<int32_t> tile_slots_, nviews_, tile_count_, tile_dropped_;
-    DeviceArray<float> tile_lbox_, tile_dets_;
-    DeviceArray<uint64_t> views_total_;
+    int device_ = 0;
     DevicePose pose_;
     DeviceFilter filter_;                 // two state buffers of streams x slots rows
     std::optional<float> prev_elapsed_;   // the previous step's `elapsed`: its estimates' (nullopt: dt)
     std::vector<std::vector<Detection>> injected_;
-    // recognition: two state / embedding buffers of streams x slots rows that swap after each step
-    // (id_flipped_: [1] holds the current state), and the packed batch of the due objects
-    int device_ = 0;
-    std::unique_ptr<FaceEmbedder> embedder_;
-    const Gallery *gallery_ = nullptr;
-    zr_identity_cfg icfg_{};
-    bool id_flipped_ = false;
-    bool id_ran_ = false;  // a step has written the identity buffers since set_recognition
-    DeviceArray<zr_identity_state> id_state_[2];
-    DeviceArray<float> id_emb_[2], id_dense_emb_, id_best_dist_;
-    DeviceArray<int32_t> id_due_, id_due_of_, id_ndue_, id_valid_, id_best_idx_;
-    DeviceArray<zr_view_desc> id_views_, id_due_views_;
-    DeviceArray<uint64_t> id_total_;
-    Gallery *enrol_ = nullptr;           // gallery_, when enrolment is on
-    uint32_t enrol_min_ = 1;
-    DeviceArray<uint64_t> enrol_counts_;  // [0] rows appended, [1] candidates dropped
-    uint32_t template_cap_ = 1;          // > 1: smoothing is on
-    DeviceArray<float> id_query_;        // the blended rows, sized like id_dense_emb_ at the first step that needs it
-    Gallery *refine_ = nullptr;          // gallery_, when refinement is on
-    uint32_t refine_max_ = 64;
-    float refine_threshold_ = NAN;       // NaN: the identity threshold at each step
-    DeviceArray<uint64_t> refine_total_; // [0] contributions applied
-    Gallery *written() const { return enrol_ ? enrol_ : refine_; }  // the gallery this tracker's steps write
-    // eye refinement: 2 entries per slot (left, right), the packed batch and the atlas it is cropped into
-    std::shared_ptr<const Cnn> eye_cnn_;
-    zr_eye_cfg ecfg_{};
-    bool eye_on_ = false;
-    bool eye_ran_ = false;  // a step has written the eye buffers since it was switched on
-    DeviceArray<int32_t> eye_flag_, eye_due_of_, eye_count_, eye_due_valid_, eye_valid_;
-    DeviceArray<zr_view_desc> eye_views_, eye_due_views_, eye_cells_;
-    DeviceArray<float> eye_crop_, eye_out_[2], eye_lm_, eye_diam_;
-    DeviceArray<uint8_t> eye_atlas_;
-    DeviceArray<uint64_t> eye_total_;
-    // the packed export: the snapshot's device records, its small page-locked read-back ([0] count,
-    // [1 ..] stream offsets, then the gallery's size with enrolment), and objects_packed()'s staging
-    struct Snapshot {
-        bool pending = false, pose = false, identity = false, eyes = false, enrol = false;
-        void *event = nullptr, *copy_stream = nullptr;
-        DeviceArray<int32_t> count, offsets, eye_valid;
-        DeviceArray<zr_export_header> header;
-        DeviceArray<float> lm, emb, eye_diam, eye_crop, eye_lm;
-        DeviceArray<zr_pose> pose_out;
-        DeviceArray<zr_export_identity> ident;
-        PinnedArray<int32_t> h_small, h_eye_valid;
-        PinnedArray<zr_export_header> h_header;
-        PinnedArray<float> h_lm, h_emb, h_eye_diam, h_eye_crop, h_eye_lm;
-        PinnedArray<zr_pose> h_pose;
-        PinnedArray<zr_export_identity> h_ident;
-        std::vector<uint64_t> person;
-    } snap_;
+    // the optional stages (multi_stages.h); members, so the destructor has synchronised the stream
+    // before their buffers are freed
+    MultiIdentity identity_;
+    MultiEyes eyes_;
+    MultiTiles tiles_;
+    MultiExport export_;
 };
 
 }  // namespace zh

@@ -1,6 +1,8 @@
 // device_tracker.cpp -- see device_tracker.h.
 #include "device_tracker.h"
 
+#include <algorithm>
+
 namespace zh {
 
 int track_kind(NetworkKind k) {
@@ -91,6 +93,48 @@ std::vector<zr_pose> DevicePose::read(size_t n, void *stream) {
     if (n) check(zr_memcpy_async(h.data(), out.ptr, n * sizeof(zr_pose), 1, stream));
     check(zr_stream_synchronize(stream));
     return h;
+}
+
+void apply_injected_detections(void *stream, size_t n, size_t dcap, int32_t *d_count, int32_t *d_pending,
+                               float *d_dets, std::vector<std::vector<Detection>> &injected) {
+    bool any = false;
+    for (auto &v : injected) any = any || !v.empty();
+    if (!any) return;
+    check(zr_stream_synchronize(stream));
+    std::vector<int32_t> cnt(n), pend(n);
+    std::vector<float> d(n * dcap * 20, 0.f);
+    check(zr_memcpy_async(cnt.data(), d_count, n * 4, 1, stream));
+    check(zr_memcpy_async(pend.data(), d_pending, n * 4, 1, stream));
+    check(zr_memcpy_async(d.data(), d_dets, d.size() * 4, 1, stream));
+    check(zr_stream_synchronize(stream));
+    for (size_t s = 0; s < n; s++) {
+        if (injected[s].empty()) continue;
+        // the host tracker's order: the injected detections, then the detector's finished result
+        std::vector<float> own;
+        const int no = pend[s] ? std::min(cnt[s], (int32_t)dcap) : 0;
+        own.assign(d.begin() + s * dcap * 20, d.begin() + (s * dcap + no) * 20);
+        cnt[s] = 0;
+        pend[s] = 1;
+        for (const Detection &det : injected[s]) {
+            if ((size_t)cnt[s] >= dcap) break;
+            float *r = d.data() + (s * dcap + cnt[s]) * 20;
+            std::fill(r, r + 20, 0.f);
+            r[0] = det.confidence;
+            r[1] = det.angle;
+            r[2] = det.rect.center().x;
+            r[3] = det.rect.center().y;
+            r[4] = det.rect.width();
+            r[5] = det.rect.height();
+            cnt[s]++;
+        }
+        for (int k = 0; k < no && (size_t)cnt[s] < dcap; k++, cnt[s]++)
+            std::copy(own.begin() + k * 20, own.begin() + (k + 1) * 20, d.begin() + (s * dcap + cnt[s]) * 20);
+        injected[s].clear();
+    }
+    check(zr_memcpy_async(d_count, cnt.data(), n * 4, 0, stream));
+    check(zr_memcpy_async(d_pending, pend.data(), n * 4, 0, stream));
+    check(zr_memcpy_async(d_dets, d.data(), d.size() * 4, 0, stream));
+    check(zr_stream_synchronize(stream));
 }
 
 DeviceTracker::DeviceTracker(LandmarkNetwork net, int device, float padding, float loss_thresh)

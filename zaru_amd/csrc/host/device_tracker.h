@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 
+#include "detection.h"
 #include "landmark.h"
 
 namespace zh {
@@ -59,6 +60,7 @@ struct DevicePose {
     DevicePose &operator=(const DevicePose &) = delete;
     ~DevicePose();
     bool on() const { return ref != nullptr; }
+    bool has_result(size_t n) const { return on() && ran && out.n >= n; }  // a step wrote n streams' records
     // replace the reference (n x 3 floats; empty: off); throws when the network has fewer landmarks
     void set(const std::vector<float> &points, bool flip_y, size_t num_landmarks, void *stream);
     // the pose of `n` streams' landmarks (n x num_landmarks x 3) on `stream`
@@ -67,6 +69,13 @@ struct DevicePose {
     // the last step's records (synchronises `stream`)
     std::vector<zr_pose> read(size_t n, void *stream);
 };
+
+// The detecting loops' test hook (HandTracker::inject_detections): where `injected[s]` is not empty,
+// its detections go ahead of the detector's result that stream s's next step consumes (the host
+// tracker's order) and the list is cleared.  `n` streams of `dcap` records of 20 floats, their counts
+// and pending flags on the device; synchronises `stream`.  Nothing injected: nothing is done.
+void apply_injected_detections(void *stream, size_t n, size_t dcap, int32_t *d_count, int32_t *d_pending,
+                               float *d_dets, std::vector<std::vector<Detection>> &injected);
 
 class DeviceTracker {
   public:

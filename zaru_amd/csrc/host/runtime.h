@@ -51,6 +51,12 @@ struct DeviceArray {
     }
 };
 
+// several arrays (device or page-locked, of any element types) of one length
+template <typename... A>
+void resize_all(size_t count, A &...arrays) {
+    (arrays.resize(count), ...);
+}
+
 // Page-locked host array: device<->host copies into it stay asynchronous.
 template <typename T>
 struct PinnedArray {
