@@ -560,6 +560,8 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
  *      zr_identity_enrol_async here: the unknown objects become gallery rows)
  *     (with templates: zr_identity_blend_async before the match, which then reads its query rows, as
  *      the commit does; with refined rows: zr_identity_refine_async between commit and enrolment)
+ *     (with the quality gate, below: zr_identity_quality_async between select and compact, and
+ *      zr_identity_quality_mask_async after the commit, whose list refine and enrol then read)
  * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
  * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
  * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
@@ -697,6 +699,89 @@ int zr_identity_refine_async(const zr_identity_cfg *cfg, size_t n, const int32_t
                              uint32_t max_samples, float update_threshold, uint64_t *d_refined_total,
                              void *hip_stream);
 
+/* ---- Face quality gate of the recognition leg ------------------------------------------------
+ * An opt-in stage between zr_identity_select_async and zr_identity_compact_async: what the
+ * embedding network is about to see of every due object is measured first, an object whose crop
+ * misses the embed tier is not embedded this step (it stays due), and one that is embedded but
+ * misses the stricter learn tier is kept out of enrolment and gallery refinement.
+ * The measurement of a crop d (the zr_view_desc zr_identity_select_async built) on frame f, over the
+ * embedder's input grid ow x oh:
+ *     luma      grid pixel (x, y) samples the frame pixel the preprocessing samples for it (the
+ *               stem's lookup, bit for bit).  Inside the frame its luma is the integer
+ *               Y = (77 R + 150 G + 29 B + 128) >> 8; outside (Color::NONE) it is marked outside.
+ *     inside    (float)n_in / (float)(ow * oh), n_in the grid pixels inside the frame
+ *     size      fminf(d.view_w, d.view_h): the crop's shorter side in frame pixels
+ *     sharpness the variance of Lap = 4 Y(x, y) - Y(x-1, y) - Y(x+1, y) - Y(x, y-1) - Y(x, y+1) over the
+ *               interior grid pixels (1 <= x <= ow - 2, 1 <= y <= oh - 2) whose five taps are all inside:
+ *               with n their number, s1 = sum Lap (int64) and s2 = sum Lap^2 (uint64),
+ *               (float)((double)(n s2 - s1 s1) / (double)(n n)), and +0 when n == 0.  Integer up to the
+ *               one f64 division: independent of the summation order, the same bits on host and device.
+ *     frontal   rot[8] of the row's zr_pose of this step when d_pose is given and its valid != 0,
+ *               else NaN: the cosine of the out-of-plane tilt, whatever the roll.
+ * The grid sees what the network sees: under heavy down-sampling its nearest-neighbour lookup
+ * aliases, so sharpness is a measure of the network's input, not of the native-resolution face.
+ * A tier is four minima; -inf skips its criterion, otherwise the criterion passes iff value >= min
+ * (a NaN value fails).  LEARN requires EMBED and every criterion of the learn tier.  The defaults a
+ * caller picks are settings, not measurements. */
+typedef struct {
+    float size, inside, sharpness, frontal;
+    uint32_t flags;    /* ZR_QUALITY_* */
+    uint32_t rejected; /* consecutive measurements that missed the embed tier; 0 after a pass */
+    uint32_t samples;  /* n of the sharpness */
+    uint32_t reserved; /* 0 */
+} zr_face_quality;     /* 32 bytes; the default record is all zero */
+#define ZR_QUALITY_MEASURED 1u
+#define ZR_QUALITY_EMBED 2u            /* passed the embed tier */
+#define ZR_QUALITY_LEARN 4u            /* and the learn tier */
+#define ZR_QUALITY_FAIL_SIZE 16u       /* the embed tier's criteria that failed */
+#define ZR_QUALITY_FAIL_INSIDE 32u
+#define ZR_QUALITY_FAIL_SHARPNESS 64u
+#define ZR_QUALITY_FAIL_FRONTAL 128u
+#define ZR_QUALITY_MAX_PIXELS 16384    /* ow * oh */
+typedef struct {
+    float min_size, min_inside, min_sharpness, min_frontal;
+} zr_quality_tier;
+typedef struct {
+    int slots;  /* K: slots per stream, 1..64 */
+    int ow, oh; /* the embedding network's input (112 x 112) */
+    zr_quality_tier embed, learn;
+} zr_quality_cfg;
+/* For row i the incoming record is row (i / slots) * slots + d_src[i] of d_in when d_state[i].tracked
+ * != 0 and d_src[i] lies in [0, slots), else the default record: it follows the object as its
+ * zr_identity_state does.  A row with d_due[i] == 0 copies it to d_out[i].  A due row is measured
+ * (d_views[i] on frame d_views[i].frame of `frames`; an index >= n_frames samples Color::NONE
+ * everywhere) and d_out[i] = the measurement with
+ *     a pass of the embed tier: flags = MEASURED | EMBED (| LEARN), rejected = 0, d_due[i] stays 1;
+ *     a failure: flags = MEASURED | the FAIL bits, rejected = min(incoming rejected + 1, 0xffffffff),
+ *                d_due[i] = 0.
+ * *d_measured_total += the rows measured, *d_rejected_total += those that failed (either may be
+ * NULL; integer atomics -- no float is accumulated atomically).  d_pose may be NULL.  The frame table
+ * travels in the launch arguments, 64 frames a launch: nothing is allocated or copied.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL required pointer, n == 0 or above
+ * 2^24, slots outside 1..64, n not a multiple of slots, ow or oh < 1, ow * oh > 16384, a NaN minimum,
+ * d_in == d_out, a tier with min_frontal > -inf while d_pose is NULL, no frames or an empty frame. */
+int zr_identity_quality_async(const zr_quality_cfg *cfg, const zr_frame *frames, size_t n_frames,
+                              const zr_track_state *d_state, size_t n, const int32_t *d_src,
+                              const zr_view_desc *d_views, const zr_pose *d_pose, const zr_face_quality *d_in,
+                              zr_face_quality *d_out, int32_t *d_due, uint64_t *d_measured_total,
+                              uint64_t *d_rejected_total, void *hip_stream);
+/* d_due_of_learn[i] = d_due_of[i] when that is >= 0 and d_quality[i].flags has ZR_QUALITY_LEARN, else
+ * -1; *d_held_total += the rows with d_due_of[i] >= 0 that were held back (may be NULL).
+ * zr_identity_enrol_async and zr_identity_refine_async are then handed d_due_of_learn in place of
+ * d_due_of; blend, match and commit keep the unmasked list (a template takes every embedding that
+ * was good enough to match on).  An object whose only matches were below the learn tier therefore
+ * does not receive ZR_IDENTITY_EVER_KNOWN from those steps -- a weak match is weak evidence -- and
+ * may be enrolled later from a good crop that matches nobody.
+ * Refused: a NULL pointer other than d_held_total, n == 0 or above 2^24. */
+int zr_identity_quality_mask_async(size_t n, const int32_t *d_due_of, const zr_face_quality *d_quality,
+                                   int32_t *d_due_of_learn, uint64_t *d_held_total, void *hip_stream);
+/* The same measurement and tiers on the host, for one crop of one host frame: *out as
+ * zr_identity_quality_async writes it for a due row whose incoming record is the default (rejected
+ * is 0 or 1).  cfg->slots is not read; pose may be NULL.  Refused: a NULL cfg, frame, view or out, an
+ * empty frame, ow or oh < 1, ow * oh > 16384, a NaN minimum. */
+int zr_face_quality_host(const zr_quality_cfg *cfg, const zr_frame *frame, const zr_view_desc *view,
+                         const zr_pose *pose, zr_face_quality *out);
+
 /* ---- Iris and eye-contour refinement of the tracked faces inside the multi-object loop -----
  * The reference has the two halves of the cascade -- FaceMeshV1::left_eye / right_eye
  * (face/landmark/mediapipe.rs:162-192) and EyeNetwork on a cropped left eye, a right eye by
@@ -797,6 +882,7 @@ int zr_eye_commit_async(const zr_eye_cfg *cfg, size_t n, const int32_t *d_due_of
 #define ZR_EXPORT_IDENTITY 2u  /* the object has been embedded: identity and embedding are its own */
 #define ZR_EXPORT_EYE_LEFT 4u  /* the left eye was valid */
 #define ZR_EXPORT_EYE_RIGHT 8u /* the right eye was valid */
+#define ZR_EXPORT_QUALITY 16u  /* the quality record was copied (the quality group is given) */
 typedef struct {
     uint64_t id;       /* the object's id */
     int32_t stream;    /* s */
@@ -842,6 +928,14 @@ typedef struct {
 } zr_multi_export_args;
 int zr_multi_export_async(const zr_multi_export_args *args, size_t n_streams, size_t slots, size_t num_landmarks,
                           void *hip_stream);
+/* The same export with one more optional group, the quality gate's records: d_quality ([rows], slot r's
+ * record, as the identity's) copied bit for bit to d_out_quality ([rows], the first *d_count), and
+ * ZR_EXPORT_QUALITY set in every header.  The group travels beside zr_multi_export_args, whose layout
+ * stays as it is; with both pointers NULL this is zr_multi_export_async.  Refused as that is, and when
+ * only one of the two is given. */
+int zr_multi_export_quality_async(const zr_multi_export_args *args, const zr_face_quality *d_quality,
+                                  zr_face_quality *d_out_quality, size_t n_streams, size_t slots,
+                                  size_t num_landmarks, void *hip_stream);
 
 /* ---- JPEG frame source --------------------------------------------------
  * Replaces decode_jpeg (crates/zaru-image/src/jpeg.rs:107-182) for its libjpeg-turbo backend

@@ -101,6 +101,27 @@ class EyeCfg(C.Structure):
                 ("in_w", C.c_int), ("in_h", C.c_int), ("crop_grow", C.c_float)]
 
 
+class FaceQuality(C.Structure):
+    """zr_face_quality: the quality gate's record of one object (32 bytes); the default is all zero."""
+    _fields_ = [("size", C.c_float), ("inside", C.c_float), ("sharpness", C.c_float), ("frontal", C.c_float),
+                ("flags", C.c_uint32), ("rejected", C.c_uint32), ("samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class QualityTier(C.Structure):
+    """zr_quality_tier: four minima; -inf skips a criterion."""
+    _fields_ = [("min_size", C.c_float), ("min_inside", C.c_float), ("min_sharpness", C.c_float),
+                ("min_frontal", C.c_float)]
+
+
+class QualityCfg(C.Structure):
+    """zr_quality_cfg."""
+    _fields_ = [("slots", C.c_int), ("ow", C.c_int), ("oh", C.c_int), ("embed", QualityTier), ("learn", QualityTier)]
+
+
+QUALITY_MEASURED, QUALITY_EMBED, QUALITY_LEARN = 1, 2, 4
+QUALITY_FAIL_SIZE, QUALITY_FAIL_INSIDE, QUALITY_FAIL_SHARPNESS, QUALITY_FAIL_FRONTAL = 16, 32, 64, 128
+
+
 class ExportHeader(C.Structure):
     """zr_export_header: the fixed part of one record of zr_multi_export_async (48 bytes)."""
     _fields_ = [("id", C.c_uint64), ("stream", C.c_int32), ("slot", C.c_int32), ("roi", C.c_float * 5),
@@ -112,12 +133,13 @@ class ExportIdentity(C.Structure):
     _fields_ = [("row", C.c_int32), ("distance", C.c_float), ("embeddings", C.c_uint32), ("flags", C.c_uint32)]
 
 
-EXPORT_POSE, EXPORT_IDENTITY, EXPORT_EYE_LEFT, EXPORT_EYE_RIGHT = 1, 2, 4, 8
+EXPORT_POSE, EXPORT_IDENTITY, EXPORT_EYE_LEFT, EXPORT_EYE_RIGHT, EXPORT_QUALITY = 1, 2, 4, 8, 16
 
 
 class MultiExportArgs(C.Structure):
     """zr_multi_export_args: the tracker's arrays and the packed outputs, device pointers.  An optional
-    group (pose; identity; eyes) is left None when its feature is off."""
+    group (pose; identity; eyes) is left None when its feature is off.  (The quality gate's group travels
+    beside it: zr_multi_export_quality_async.)"""
     INPUTS = ("d_nobjects", "d_src", "d_ids", "d_roi", "d_state", "d_landmarks")
     POSE = ("d_pose", "d_out_pose")
     IDENTITY = ("d_id_state", "d_id_emb", "d_out_identity", "d_out_emb")
@@ -185,11 +207,15 @@ SIGNATURES = [
     ("zr_identity_enrol_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, _P, _P, _P]),
     ("zr_identity_blend_async", _I, [_P, _SZ, _P, _P, _P, _P, _U32, _P, _P]),
     ("zr_identity_refine_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, C.c_float, _P, _P]),
+    ("zr_identity_quality_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("zr_identity_quality_mask_async", _I, [_SZ, _P, _P, _P, _P, _P]),
+    ("zr_face_quality_host", _I, [_P, _P, _P, _P, _P]),
     ("zr_embed_match_count_async", _I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),
     ("zr_eye_commit_async", _I, [_P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     ("zr_multi_export_async", _I, [_P, _SZ, _SZ, _SZ, _P]),
+    ("zr_multi_export_quality_async", _I, [_P, _P, _P, _SZ, _SZ, _SZ, _P]),
     ("zr_comm_unique_id", _I, [_P]),
     ("zr_comm_create", _I, [_P, _I, _I, _I, C.POINTER(_P)]),
     ("zr_comm_destroy", None, [_P]),

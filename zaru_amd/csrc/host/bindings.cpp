@@ -75,6 +75,19 @@ py::array_t<float> f32_array(const float *v, std::vector<py::ssize_t> shape) {
     return a;
 }
 
+// a zr_face_quality record as objects()[j]["quality"] reports it
+py::dict quality_dict(const zr_face_quality &q) {
+    py::dict d;
+    d["size"] = q.size;
+    d["inside"] = q.inside;
+    d["sharpness"] = q.sharpness;
+    d["frontal"] = q.frontal;
+    d["flags"] = q.flags;
+    d["rejected"] = q.rejected;
+    d["samples"] = q.samples;
+    return d;
+}
+
 // set_pose_reference's argument: None / empty (off) or (n, 3) float32 points
 std::vector<float> pose_reference_arg(const py::object &o) {
     if (o.is_none()) return {};
@@ -143,6 +156,44 @@ std::vector<Detection> detect_post(const std::string &net, py::array_t<float, py
 PYBIND11_MODULE(_zaru_host, m) {
     m.doc() = "Host-side mirror of Zaru's detection/landmark API over the MI355X C ABI";
     py::register_exception<ZaruError>(m, "ZaruError", PyExc_RuntimeError);
+    PYBIND11_NUMPY_DTYPE(zr_face_quality, size, inside, sharpness, frontal, flags, rejected, samples, reserved);
+    // one tier of the face quality gate: four minima, -inf skips a criterion (settings, not measurements)
+    py::class_<zr_quality_tier>(m, "FaceQualityGate")
+        .def(py::init([](float min_size, float min_inside, float min_sharpness, float min_frontal) {
+                 return zr_quality_tier{min_size, min_inside, min_sharpness, min_frontal};
+             }), py::arg("min_size") = -INFINITY, py::arg("min_inside") = -INFINITY,
+             py::arg("min_sharpness") = -INFINITY, py::arg("min_frontal") = -INFINITY)
+        .def_readwrite("min_size", &zr_quality_tier::min_size)
+        .def_readwrite("min_inside", &zr_quality_tier::min_inside)
+        .def_readwrite("min_sharpness", &zr_quality_tier::min_sharpness)
+        .def_readwrite("min_frontal", &zr_quality_tier::min_frontal);
+    // zr_face_quality_host: the gate's measurement of `view` (a ViewData) of a host RGBA image on an
+    // ow x oh grid; pose: None or the 21 floats of a zr_pose record; the tiers default to all -inf
+    m.def("face_quality", [](py::array_t<uint8_t, py::array::c_style> image, const ViewData &view, int ow, int oh,
+                             const py::object &pose, const py::object &embed, const py::object &learn) {
+        const Image im = host_image(image);
+        const zr_frame f{im.rgba, im.width, im.height, im.row_stride};
+        const zr_view v = to_zr_view(view);
+        zr_view_desc d;
+        check(zr_view_describe(&v, 1, 0, &d));
+        const zr_quality_tier skip{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        zr_quality_cfg cfg{};
+        cfg.slots = 1;
+        cfg.ow = ow;
+        cfg.oh = oh;
+        cfg.embed = embed.is_none() ? skip : embed.cast<zr_quality_tier>();
+        cfg.learn = learn.is_none() ? cfg.embed : learn.cast<zr_quality_tier>();
+        zr_pose p{};
+        if (!pose.is_none()) {
+            auto a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(pose);
+            if (!a || a.size() != 21) throw ZaruError(ZR_ERR_SHAPE, "pose must be None or the 21 floats of a zr_pose");
+            std::memcpy(&p, a.data(), sizeof(p));
+        }
+        zr_face_quality q{};
+        check(zr_face_quality_host(&cfg, &f, &d, pose.is_none() ? nullptr : &p, &q));
+        return quality_dict(q);
+    }, py::arg("image"), py::arg("view"), py::arg("ow"), py::arg("oh"), py::arg("pose") = py::none(),
+       py::arg("embed_tier") = py::none(), py::arg("learn_tier") = py::none());
 
     py::class_<Rect>(m, "Rect")
         .def_static("from_center", &Rect::from_center)
@@ -569,6 +620,18 @@ PYBIND11_MODULE(_zaru_host, m) {
         }, py::arg("gallery"), py::arg("max_samples") = 64, py::arg("update_threshold") = NAN, py::keep_alive<1, 2>())
         .def("gallery_refinement", &DeviceMultiTracker::gallery_refinement)
         .def("refined_total", &DeviceMultiTracker::refined_total)
+        // the face quality gate: FaceQualityGate tiers (learn: the embed tier when None); embed None: off
+        .def("set_identity_quality", [](DeviceMultiTracker &t, const py::object &embed, const py::object &learn) {
+            if (embed.is_none()) return t.set_identity_quality(nullptr);
+            const zr_quality_tier e = embed.cast<zr_quality_tier>();
+            if (learn.is_none()) return t.set_identity_quality(&e);
+            const zr_quality_tier l = learn.cast<zr_quality_tier>();
+            t.set_identity_quality(&e, &l);
+        }, py::arg("embed_tier"), py::arg("learn_tier") = py::none())
+        .def("identity_quality", &DeviceMultiTracker::identity_quality)
+        .def("quality_measured_total", &DeviceMultiTracker::quality_measured_total)
+        .def("quality_rejected_total", &DeviceMultiTracker::quality_rejected_total)
+        .def("quality_held_back_total", &DeviceMultiTracker::quality_held_back_total)
         // iris and eye-contour refinement of every tracked face (FaceMesh V1 / V2)
         .def("set_eye_refinement", &DeviceMultiTracker::set_eye_refinement, py::arg("on"))
         .def("eye_refinement", &DeviceMultiTracker::eye_refinement)
@@ -633,6 +696,12 @@ PYBIND11_MODULE(_zaru_host, m) {
                 d["identity_present"] = present;
                 d["embedding"] = f32_array(p.embedding, {c, (py::ssize_t)EMBEDDING_DIM});
             }
+            // the zr_face_quality records as a structured array (zaru_amd._lib.FaceQuality's layout)
+            if (p.quality) {
+                py::array_t<zr_face_quality> q(c);
+                if (c) std::memcpy(q.mutable_data(), p.quality, (size_t)c * sizeof(zr_face_quality));
+                d["quality"] = q;
+            }
             if (p.eye_valid) {
                 py::array_t<int32_t> valid({c, (py::ssize_t)2});
                 std::memcpy(valid.mutable_data(), p.eye_valid, (size_t)valid.size() * 4);
@@ -682,6 +751,8 @@ PYBIND11_MODULE(_zaru_host, m) {
                     }
                     d["eyes"] = eyes;
                 }
+                // present only while the quality gate is on and a step has run it
+                if (o.quality) d["quality"] = quality_dict(*o.quality);
                 out.append(d);
             }
             return out;

@@ -158,6 +158,11 @@ void DeviceMultiTracker::set_gallery_refinement(Gallery *gallery, uint32_t max_s
     identity_.set_refinement(ctx(), gallery, max_samples, update_threshold);
 }
 
+void DeviceMultiTracker::set_identity_quality(const zr_quality_tier *embed, const zr_quality_tier *learn) {
+    export_.pending = false;  // a snapshot's arrays are those of the features it was taken with
+    identity_.set_quality(ctx(), embed, learn);
+}
+
 void DeviceMultiTracker::set_eye_crop_grow(float g) {
     if (!(g >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "eye crop grow factor must be >= 0");
     eyes_.cfg.crop_grow = g;
@@ -195,6 +200,8 @@ void DeviceMultiTracker::frame_size(uint32_t W, uint32_t H) {
 void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, std::optional<float> elapsed) {
     if (frames.size() != n_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one frame per stream");
     if (identity_.on() && std::isnan(now_ms)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "recognition needs a frame clock");
+    if (identity_.on() && identity_.quality.on() && identity_.quality.needs_pose() && !pose_.on())
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "a quality tier with a frontal minimum needs a pose reference");
     // refused while another tracker's writing steps may be in flight
     if (Gallery *g = identity_.written()) g->begin_enrol(this);
     // both checked before anything is enqueued: this frame's elapsed, and the previous frame's that
@@ -241,7 +248,8 @@ void DeviceMultiTracker::step(const std::vector<Image> &frames, double now_ms, s
         // 2. the head pose of the slots tracked just now, while pose, landmarks and state share a slot
         if (pose_.on()) pose_.enqueue(state_.ptr, lm_out_.ptr, nv, (size_t)lm_net_.num_landmarks, stream_);
         // and, at the same place for the same reason, who they are
-        if (identity_.on()) identity_.enqueue(c, zf, now_ms, state_.ptr, lm_out_.ptr, src_.ptr);
+        if (identity_.on())
+            identity_.enqueue(c, zf, now_ms, state_.ptr, lm_out_.ptr, src_.ptr, pose_.on() ? pose_.out.ptr : nullptr);
         // and the eyes of the faces tracked just now
         if (eyes_.on()) eyes_.enqueue(c, zf, state_.ptr, lm_out_.ptr);
     }
@@ -317,6 +325,9 @@ uint64_t DeviceMultiTracker::identity_images() { return read_u64(identity_.total
 uint64_t DeviceMultiTracker::enrolled_total() { return read_u64(identity_.enrol_counts, 0); }
 uint64_t DeviceMultiTracker::enrol_dropped() { return read_u64(identity_.enrol_counts, 1); }
 uint64_t DeviceMultiTracker::refined_total() { return read_u64(identity_.refine_total); }
+uint64_t DeviceMultiTracker::quality_measured_total() { return read_u64(identity_.quality.counts, 0); }
+uint64_t DeviceMultiTracker::quality_rejected_total() { return read_u64(identity_.quality.counts, 1); }
+uint64_t DeviceMultiTracker::quality_held_back_total() { return read_u64(identity_.quality.counts, 2); }
 uint64_t DeviceMultiTracker::eye_images() { return read_u64(eyes_.total); }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {
@@ -345,6 +356,11 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
         iemb.resize((size_t)K * EMBEDDING_DIM);
         check(zr_memcpy_async(ist.data(), identity_.state().ptr + s * K, sizeof(zr_identity_state) * K, 1, stream_));
         check(zr_memcpy_async(iemb.data(), identity_.emb().ptr + s * K * EMBEDDING_DIM, iemb.size() * 4, 1, stream_));
+    }
+    std::vector<zr_face_quality> qual;
+    if (identity_.quality_result()) {  // written per slot before the bookkeeping, like the identity
+        qual.resize(K);
+        check(zr_memcpy_async(qual.data(), identity_.quality_state().ptr + s * K, sizeof(zr_face_quality) * K, 1, stream_));
     }
     std::vector<int32_t> evalid;
     std::vector<float> ediam, ecrop, elm;
@@ -377,6 +393,7 @@ std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s
             d.identity = Identity{identity_.gallery->id_of(is.row), is.distance, is.embeddings,
                                   std::vector<float>(e, e + EMBEDDING_DIM), (is.flags & ZR_IDENTITY_ENROLLED) != 0};
         }
+        if (!qual.empty()) d.quality = qual[src[j]];
         if (!evalid.empty()) {
             Eyes eyes;
             for (int side = 0; side < 2; side++) {

@@ -129,6 +129,19 @@ class DeviceMultiTracker {
     void set_gallery_refinement(Gallery *gallery, uint32_t max_samples = 64, float update_threshold = NAN);
     bool gallery_refinement() const { return identity_.refine != nullptr; }
     uint64_t refined_total();   // contributions this tracker's steps applied, summed
+    // The face quality gate (MultiQuality in multi_stages.h; zr_identity_quality_async in
+    // include/zaru_hip.h has the measurement): a due object whose crop misses `embed` is not embedded
+    // this step and stays due; one that is embedded but misses `learn` (default: the embed tier) is
+    // matched, and neither enrolled nor a sample of its gallery row.  A minimum of -inf skips its
+    // criterion, a NaN minimum is refused.  Needs recognition; every set_recognition turns it off;
+    // nullptr for `embed` turns it off.  Every call resets every object's quality record.  A tier with
+    // min_frontal > -inf needs a pose reference: without one step() throws before it enqueues anything,
+    // so the objects are not silently starved.  The tiers are settings, chosen and not tuned.
+    void set_identity_quality(const zr_quality_tier *embed, const zr_quality_tier *learn = nullptr);
+    bool identity_quality() const { return identity_.quality.on(); }
+    uint64_t quality_measured_total();   // crops measured, summed (0 before set_identity_quality)
+    uint64_t quality_rejected_total();   // of those, the ones that missed the embed tier
+    uint64_t quality_held_back_total();  // objects embedded but kept out of enrolment and refinement
     // Eye refinement of every tracked face, every step (default off).  Refused unless the
     // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
     // step enqueues what it did without, and objects() reports no eyes.
@@ -170,6 +183,7 @@ class DeviceMultiTracker {
         std::optional<zr_pose> pose;   // with a pose reference set
         std::optional<Identity> identity;  // with recognition set, once the object was embedded
         std::optional<Eyes> eyes;      // with eye refinement on, once a step has run it
+        std::optional<zr_face_quality> quality;  // with the quality gate on, once a step has run it
     };
     // after synchronize(): stream s's objects that have a result, in slot order
     std::vector<ObjectData> objects(size_t s);
@@ -184,7 +198,7 @@ class DeviceMultiTracker {
     using PackedObjects = MultiPackedObjects;  // count, stream_offsets and the arrays (multi_stages.h)
     // The pending snapshot's records, or -- none pending -- those of a snapshot taken now: waits for the
     // snapshot's event only (not for steps enqueued since), then copies exactly `count` rows of each
-    // present array to page-locked staging on a stream of its own, with one wait: at most nine
+    // present array to page-locked staging on a stream of its own, with one wait: at most ten
     // copies, however many streams.  The arrays are the tracker's and stay valid until the next
     // objects_packed().  Consumes the snapshot.
     PackedObjects objects_packed();

@@ -58,6 +58,7 @@ void MultiIdentity::set(const MultiCtx &c, const std::vector<uint8_t> &model, co
     c.synchronize();  // the last step's launches still read the network and the gallery
     enrol = refine = nullptr;  // enrolment, refinement and smoothing belong to the gallery they were set for
     template_cap = 1;
+    quality.enabled = quality.ran = false;  // and the quality gate to the embedder
     embedder = std::move(emb);
     gallery = embedder ? g : nullptr;
     ran = false;
@@ -132,18 +133,54 @@ void MultiIdentity::set_refinement(const MultiCtx &c, Gallery *g, uint32_t max_s
     refine_threshold = update_threshold;
 }
 
+void MultiIdentity::set_quality(const MultiCtx &c, const zr_quality_tier *embed, const zr_quality_tier *learn) {
+    if (!embed) {
+        c.synchronize();
+        quality.enabled = quality.ran = false;
+        return;
+    }
+    if (!on()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the quality gate needs recognition (set_recognition)");
+    const zr_quality_tier l = learn ? *learn : *embed;
+    for (const zr_quality_tier *t : {embed, &l})
+        if (std::isnan(t->min_size) || std::isnan(t->min_inside) || std::isnan(t->min_sharpness) ||
+            std::isnan(t->min_frontal))
+            throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "a quality minimum is NaN (-inf skips a criterion)");
+    const Cnn &ec = embedder->cnn();
+    if ((uint64_t)ec.input_width() * ec.input_height() > ZR_QUALITY_MAX_PIXELS)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the quality gate measures input grids of up to 16384 pixels");
+    c.synchronize();  // the last step's launches still read the records
+    const size_t nv = c.rows();
+    resize_all(nv, quality.recs[0], quality.recs[1], quality.due_of_learn);
+    zero_once(quality.counts, 3, c.stream);
+    // every object starts over: the default record in both buffers
+    for (int b = 0; b < 2; b++) check(zr_memset_async(quality.recs[b].ptr, 0, nv * sizeof(zr_face_quality), c.stream));
+    check(zr_stream_synchronize(c.stream));
+    quality.cfg.slots = c.slots;
+    quality.cfg.ow = (int)ec.input_width();
+    quality.cfg.oh = (int)ec.input_height();
+    quality.cfg.embed = *embed;
+    quality.cfg.learn = l;
+    quality.enabled = true;
+    quality.ran = false;
+}
+
 void MultiIdentity::frame_size(const MultiCtx &c, const zr_view_desc &det_tmpl) {
     const auto rows = upload_frame_views(due_views.ptr, &det_tmpl, 1, c.rows(), (size_t)c.slots, c.stream);
     check(zr_stream_synchronize(c.stream));
 }
 
 void MultiIdentity::enqueue(const MultiCtx &c, const std::vector<zr_frame> &frames, double now_ms,
-                            const zr_track_state *d_state, const float *d_landmarks, const int32_t *d_src) {
+                            const zr_track_state *d_state, const float *d_landmarks, const int32_t *d_src,
+                            const zr_pose *d_pose) {
     const size_t nv = c.rows();
     void *stream = c.stream;
     const int in = flipped ? 1 : 0, o = 1 - in;
     check(zr_identity_select_async(&cfg, d_state, nv, d_landmarks, d_src, now_ms, states[in].ptr, embs[in].ptr,
                                    states[o].ptr, embs[o].ptr, due.ptr, views.ptr, stream));
+    if (quality.on())  // the due rows measured; those that miss the embed tier leave the due list
+        check(zr_identity_quality_async(&quality.cfg, frames.data(), c.streams, d_state, nv, d_src, views.ptr, d_pose,
+                                        quality.recs[in].ptr, quality.recs[o].ptr, due.ptr, quality.counts.ptr,
+                                        quality.counts.ptr + 1, stream));
     check(zr_identity_compact_async(due.ptr, views.ptr, nv, due_views.ptr, due_of.ptr, ndue.ptr, valid.ptr, total.ptr,
                                     stream));
     const Cnn &ec = embedder->cnn();
@@ -169,14 +206,22 @@ void MultiIdentity::enqueue(const MultiCtx &c, const std::vector<zr_frame> &fram
     }
     check(zr_identity_commit_async(&cfg, nv, due_of.ptr, best_idx.ptr, best_dist.ptr, q, now_ms, states[o].ptr,
                                    embs[o].ptr, stream));
+    // the enrolment and the refinement learn from the rows that passed the learn tier only
+    const int32_t *learn_of = due_of.ptr;
+    if (quality.on()) {
+        check(zr_identity_quality_mask_async(nv, due_of.ptr, quality.recs[o].ptr, quality.due_of_learn.ptr,
+                                             quality.counts.ptr + 2, stream));
+        learn_of = quality.due_of_learn.ptr;
+        quality.ran = true;
+    }
     if (refine)
-        check(zr_identity_refine_async(&cfg, nv, due_of.ptr, states[o].ptr, dense_emb.ptr, refine->device_rows_mut(),
+        check(zr_identity_refine_async(&cfg, nv, learn_of, states[o].ptr, dense_emb.ptr, refine->device_rows_mut(),
                                        refine->device_updates(), refine->device_count(), refine->capacity(),
                                        EMBEDDING_DIM, refine_max,
                                        std::isnan(refine_threshold) ? cfg.threshold : refine_threshold,
                                        refine_total.ptr, stream));
     if (enrol)
-        check(zr_identity_enrol_async(&cfg, nv, due_of.ptr, states[o].ptr, embs[o].ptr, enrol->device_rows_mut(),
+        check(zr_identity_enrol_async(&cfg, nv, learn_of, states[o].ptr, embs[o].ptr, enrol->device_rows_mut(),
                                       enrol->device_ids(), enrol->device_count(), enrol->device_next_id(),
                                       enrol->capacity(), EMBEDDING_DIM, enrol_min, enrol_counts.ptr,
                                       enrol_counts.ptr + 1, stream));
@@ -326,6 +371,7 @@ void MultiExport::snapshot(const MultiCtx &c, zr_multi_export_args a, const Devi
     identity = id.has_result();
     eyes = e.has_result();
     enrol = identity && id.enrol != nullptr;
+    quality = id.quality_result();
     // each device array with read()'s page-locked staging of the same, full size: allocated once, so
     // read()'s copies never wait for an allocation
     count.resize(1);
@@ -363,7 +409,12 @@ void MultiExport::snapshot(const MultiCtx &c, zr_multi_export_args a, const Devi
         a.d_out_eye_crop = eye_crop.ptr;
         a.d_out_eye_lm = eye_lm.ptr;
     }
-    check(zr_multi_export_async(&a, n, (size_t)c.slots, L, c.stream));
+    if (quality) {
+        resize_all(nv, qual, h_qual);
+        check(zr_multi_export_quality_async(&a, id.quality_state().ptr, qual.ptr, n, (size_t)c.slots, L, c.stream));
+    } else {
+        check(zr_multi_export_async(&a, n, (size_t)c.slots, L, c.stream));
+    }
     check(zr_memcpy_async(h_small.ptr, count.ptr, 4, 1, c.stream));
     check(zr_memcpy_async(h_small.ptr + 1, offsets.ptr, (n + 1) * 4, 1, c.stream));
     // the gallery's size as of this point of the stream: the rows the snapshot's identities can name
@@ -398,6 +449,7 @@ MultiPackedObjects MultiExport::read(const MultiCtx &c, const MultiIdentity &id)
             check(zr_memcpy_async(h_eye_crop.ptr, eye_crop.ptr, 2 * cnt * 5 * 4, 1, cs));
             check(zr_memcpy_async(h_eye_lm.ptr, eye_lm.ptr, 2 * cnt * EYE_POINTS * 3 * sizeof(float), 1, cs));
         }
+        if (quality) check(zr_memcpy_async(h_qual.ptr, qual.ptr, cnt * sizeof(zr_face_quality), 1, cs));
         check(zr_stream_synchronize(cs));
     }
     o.headers = h_header.ptr;
@@ -414,6 +466,7 @@ MultiPackedObjects MultiExport::read(const MultiCtx &c, const MultiIdentity &id)
         o.identity_id = person.data();
         o.embedding = h_emb.ptr;
     }
+    if (quality) o.quality = h_qual.ptr;
     if (eyes) {
         o.eye_valid = h_eye_valid.ptr;
         o.iris_diameter = h_eye_diam.ptr;

@@ -36,6 +36,29 @@ struct MultiCtx {
 [[nodiscard]] std::vector<float> upload_letterbox_rows(float *dst, const std::vector<Rect> &lb, size_t count,
                                                        void *stream);
 
+// The face quality gate of recognition (opt-in, MultiIdentity::set_quality; zr_identity_quality_async in
+// include/zaru_hip.h has the measurement and the tiers): a member of MultiIdentity, whose enqueue()
+// runs it.  Every object carries a quality record that follows it between slots as its identity
+// does, in two buffers that swap with the identity's.  Between a. and b. below every due object's
+// crop is measured on the embedder's input grid, and an object that misses the embed tier leaves
+// the due list: it is not embedded this step and is measured again at the next (there is no retry
+// back-off).  After e. the due list is masked (zr_identity_quality_mask_async) and f. and h. read
+// the masked list: an object that was embedded but missed the learn tier is matched and keeps its
+// template, and is neither enrolled nor a sample of its gallery row.  One consequence: such an
+// object does not get ZR_IDENTITY_EVER_KNOWN from that step, so it may be enrolled later from a good
+// crop that matches nobody -- a weak match is weak evidence.  Off, nothing of this is enqueued or
+// allocated.
+struct MultiQuality {
+    bool enabled = false;
+    bool ran = false;  // a step has written the records since the gate was switched on
+    zr_quality_cfg cfg{};
+    DeviceArray<zr_face_quality> recs[2];  // indexed like MultiIdentity::states
+    DeviceArray<int32_t> due_of_learn;     // the masked list
+    DeviceArray<uint64_t> counts;          // [0] measured, [1] rejected, [2] embedded but held back
+    bool on() const { return enabled; }
+    bool needs_pose() const { return cfg.embed.min_frontal > -INFINITY || cfg.learn.min_frontal > -INFINITY; }
+};
+
 // Recognition (opt-in, set): every object carries an identity -- the gallery row it matched, the
 // distance, how often it was embedded, its last embedding and when it is due again -- that follows
 // it between slots through the bookkeeping's `src`, as the filter state does.  Between the loop's
@@ -79,6 +102,7 @@ struct MultiIdentity {
     uint32_t refine_max = 64;
     float refine_threshold = NAN;        // NaN: the identity threshold at each step
     DeviceArray<uint64_t> refine_total;  // [0] contributions applied
+    MultiQuality quality;                // the quality gate (off by default)
 
     MultiIdentity();
     bool on() const { return embedder != nullptr; }
@@ -91,11 +115,16 @@ struct MultiIdentity {
     void set_enrolment(const MultiCtx &c, Gallery *g, uint64_t first_id, uint32_t min_embeddings);
     void set_smoothing(uint32_t cap);
     void set_refinement(const MultiCtx &c, Gallery *g, uint32_t max_samples, float update_threshold);
+    // DeviceMultiTracker::set_identity_quality; embed == nullptr: off.  Resets every object's record.
+    void set_quality(const MultiCtx &c, const zr_quality_tier *embed, const zr_quality_tier *learn);
+    bool quality_result() const { return on() && quality.on() && quality.ran; }
+    const DeviceArray<zr_face_quality> &quality_state() const { return quality.recs[flipped ? 1 : 0]; }
     // a valid view in every entry of the packed crop table, as the loop's frame_size() does for its own
     void frame_size(const MultiCtx &c, const zr_view_desc &det_tmpl);
-    // a.-h.; the gallery's rows and size as they are now (Gallery::add may have reallocated them)
+    // a.-h.; the gallery's rows and size as they are now (Gallery::add may have reallocated them).
+    // d_pose: this step's pose records, or nullptr (read by the quality gate only)
     void enqueue(const MultiCtx &c, const std::vector<zr_frame> &frames, double now_ms, const zr_track_state *d_state,
-                 const float *d_landmarks, const int32_t *d_src);
+                 const float *d_landmarks, const int32_t *d_src, const zr_pose *d_pose);
 };
 
 // Eye refinement (opt-in, set; FaceMesh V1 / V2): the iris and eye-contour points of both eyes of
@@ -186,19 +215,22 @@ struct MultiPackedObjects {
     const float *iris_diameter = nullptr;           // [count][2]
     const float *eye_crop = nullptr;                // [count][2][5]
     const float *eye_landmarks = nullptr;           // [count][2][76][3]
+    const zr_face_quality *quality = nullptr;       // [count], while the quality gate is on
 };
 
 // The packed export (kernels/export.hip): the snapshot's device records, its small page-locked
 // read-back ([0] count, [1 ..] stream offsets, then the gallery's size with enrolment), and read()'s
 // staging.  Nothing of it is allocated before the first snapshot().
 struct MultiExport {
-    bool pending = false, pose = false, identity = false, eyes = false, enrol = false;
+    bool pending = false, pose = false, identity = false, eyes = false, enrol = false, quality = false;
     void *event = nullptr, *copy_stream = nullptr;
     DeviceArray<int32_t> count, offsets, eye_valid;
     DeviceArray<zr_export_header> header;
     DeviceArray<float> lm, emb, eye_diam, eye_crop, eye_lm;
     DeviceArray<zr_pose> pose_out;
     DeviceArray<zr_export_identity> ident;
+    DeviceArray<zr_face_quality> qual;
+    PinnedArray<zr_face_quality> h_qual;
     PinnedArray<int32_t> h_small, h_eye_valid;
     PinnedArray<zr_export_header> h_header;
     PinnedArray<float> h_lm, h_emb, h_eye_diam, h_eye_crop, h_eye_lm;

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(1024) void export_scan_kernel(const ExportParams P)
                 const int r = P.src[slot0 + j];
                 if (!exported(r, P.K)) continue;
                 const int64_t from = slot0 + r;
-                uint32_t flags = P.pose ? EXPORT_POSE : 0;
+                uint32_t flags = (P.pose ? EXPORT_POSE : 0) | (P.quality ? EXPORT_QUALITY : 0);
                 if (P.ist && P.ist[from].embeddings != 0) flags |= EXPORT_IDENTITY;
                 if (P.eye_valid) {
                     if (P.eye_valid[2 * from] != 0) flags |= EXPORT_EYE_LEFT;
@@ -127,6 +127,9 @@ __global__ __launch_bounds__(256) void export_copy_kernel(const ExportParams P) 
             }
             copy_words<V4>(P.out_emb + k * IDENTITY_DIM, present ? P.emb + from * IDENTITY_DIM : nullptr, IDENTITY_DIM);
         }
+        if (P.quality)
+            copy_words<false>(P.out_quality + k * EXPORT_QUALITY_WORDS, P.quality + from * EXPORT_QUALITY_WORDS,
+                              EXPORT_QUALITY_WORDS);
         if (P.eye_valid) {
             for (int side = 0; side < 2; ++side) {
                 const bool present = (h.flags & (side ? EXPORT_EYE_RIGHT : EXPORT_EYE_LEFT)) != 0;

@@ -20,6 +20,7 @@
 #include "zr_track.h"
 #include "../kernels/procrustes_math.h"
 #include "../kernels/eye_math.h"
+#include "../kernels/quality_math.h"
 
 namespace {
 
@@ -1379,6 +1380,97 @@ int zr_identity_refine_async(const zr_identity_cfg *cfg, size_t n, const int32_t
     });
 }
 
+// ---- the face quality gate of the recognition leg (kernels/quality.hip)
+static_assert(sizeof(zr_face_quality) == sizeof(zr::quality::Record) && sizeof(zr_face_quality) == 32,
+              "zr_face_quality layout");
+static_assert(offsetof(zr_face_quality, flags) == offsetof(zr::quality::Record, flags) &&
+                  offsetof(zr_face_quality, samples) == offsetof(zr::quality::Record, samples),
+              "zr_face_quality layout");
+static_assert(sizeof(zr_quality_tier) == sizeof(zr::quality::Tier), "zr_quality_tier layout");
+static_assert(ZR_QUALITY_MEASURED == zr::quality::MEASURED && ZR_QUALITY_EMBED == zr::quality::EMBED &&
+                  ZR_QUALITY_LEARN == zr::quality::LEARN && ZR_QUALITY_FAIL_SIZE == zr::quality::FAIL_SIZE &&
+                  ZR_QUALITY_FAIL_INSIDE == zr::quality::FAIL_INSIDE &&
+                  ZR_QUALITY_FAIL_SHARPNESS == zr::quality::FAIL_SHARPNESS &&
+                  ZR_QUALITY_FAIL_FRONTAL == zr::quality::FAIL_FRONTAL,
+              "quality flags");
+static_assert(ZR_QUALITY_MAX_PIXELS == zr::quality::MAX_PIXELS, "quality grid limit");
+static_assert(offsetof(zr_pose, valid) == 4 * 7 && offsetof(zr_pose, rot) == 4 * 12, "zr_pose words the gate reads");
+
+int zr_identity_quality_async(const zr_quality_cfg *cfg, const zr_frame *frames, size_t n_frames,
+                              const zr_track_state *d_state, size_t n, const int32_t *d_src,
+                              const zr_view_desc *d_views, const zr_pose *d_pose, const zr_face_quality *d_in,
+                              zr_face_quality *d_out, int32_t *d_due, uint64_t *d_measured_total,
+                              uint64_t *d_rejected_total, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!cfg || !frames || !d_state || !d_src || !d_views || !d_in || !d_out || !d_due)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+        if (cfg->slots < 1 || cfg->slots > 64 || n % (size_t)cfg->slots != 0)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64 and divide n");
+        if (cfg->ow < 1 || cfg->oh < 1 || (int64_t)cfg->ow * cfg->oh > ZR_QUALITY_MAX_PIXELS)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the grid must be 1 x 1 .. 16384 pixels");
+        const float *mins[2] = {&cfg->embed.min_size, &cfg->learn.min_size};
+        for (const float *m : mins)
+            for (int k = 0; k < 4; k++)
+                if (m[k] != m[k]) return set_err(ZR_ERR_INVALID_ARGUMENT, "a NaN minimum");
+        if (d_in == d_out) return set_err(ZR_ERR_INVALID_ARGUMENT, "the input records must be a buffer of their own");
+        if (!d_pose && (cfg->embed.min_frontal > -INFINITY || cfg->learn.min_frontal > -INFINITY))
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "a frontal minimum needs the pose records");
+        if (n_frames == 0 || n_frames > (size_t)INT32_MAX) return set_err(ZR_ERR_INVALID_ARGUMENT, "bad frame count");
+        for (size_t i = 0; i < n_frames; i++)
+            if (!frames[i].rgba || frames[i].width == 0 || frames[i].height == 0)
+                return set_err(ZR_ERR_INVALID_ARGUMENT, "empty frame");
+        hipStream_t st = (hipStream_t)hip_stream;
+        zr::QualityParams p{};
+        p.nframes = (int)n_frames;
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.src = d_src;
+        p.views = reinterpret_cast<const zr::ViewDesc *>(d_views);
+        p.pose = reinterpret_cast<const uint32_t *>(d_pose);
+        p.in = reinterpret_cast<const zr::quality::Record *>(d_in);
+        p.out = reinterpret_cast<zr::quality::Record *>(d_out);
+        p.due = d_due;
+        p.measured_total = reinterpret_cast<unsigned long long *>(d_measured_total);
+        p.rejected_total = reinterpret_cast<unsigned long long *>(d_rejected_total);
+        p.n = (int)n;
+        p.K = cfg->slots;
+        p.ow = cfg->ow;
+        p.oh = cfg->oh;
+        std::memcpy(p.embed, &cfg->embed, sizeof(p.embed));
+        std::memcpy(p.learn, &cfg->learn, sizeof(p.learn));
+        // the frame table goes with the launch's arguments, zr::QUALITY_FRAMES frames at a time
+        for (size_t base = 0; base < n_frames; base += zr::QUALITY_FRAMES) {
+            p.base = (int)base;
+            for (size_t j = 0; j < (size_t)zr::QUALITY_FRAMES; j++) {
+                const size_t i = base + j;
+                p.frames[j] = i < n_frames ? zr::FrameDesc{frames[i].rgba, frames[i].width, frames[i].height,
+                                                           frames[i].row_stride}
+                                           : zr::FrameDesc{nullptr, 0, 0, 0};
+            }
+            zr::launch_quality_measure(p, st);
+            HIP_TRY(hipGetLastError());
+        }
+        return ZR_OK;
+    });
+}
+
+int zr_identity_quality_mask_async(size_t n, const int32_t *d_due_of, const zr_face_quality *d_quality,
+                                   int32_t *d_due_of_learn, uint64_t *d_held_total, void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!d_due_of || !d_quality || !d_due_of_learn) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+        zr::QualityMaskParams p{};
+        p.due_of = d_due_of;
+        p.q = reinterpret_cast<const zr::quality::Record *>(d_quality);
+        p.due_of_learn = d_due_of_learn;
+        p.held_total = reinterpret_cast<unsigned long long *>(d_held_total);
+        p.n = (int)n;
+        zr::launch_quality_mask(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 // ---- eye refinement of the tracked faces (kernels/eye.hip)
 static int check_eye(const zr_eye_cfg *cfg, size_t n) {
     if (!cfg) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
@@ -1495,11 +1587,13 @@ static_assert(sizeof(zr_export_identity) == sizeof(zr::ExportIdentity) && sizeof
 static_assert(sizeof(zr_pose) == 4 * zr::EXPORT_POSE_WORDS, "zr_pose words");
 static_assert(3 * ZR_EYE_POINTS == zr::EXPORT_EYE_WORDS, "eye landmark words");
 static_assert(ZR_EXPORT_POSE == zr::EXPORT_POSE && ZR_EXPORT_IDENTITY == zr::EXPORT_IDENTITY &&
-                  ZR_EXPORT_EYE_LEFT == zr::EXPORT_EYE_LEFT && ZR_EXPORT_EYE_RIGHT == zr::EXPORT_EYE_RIGHT,
+                  ZR_EXPORT_EYE_LEFT == zr::EXPORT_EYE_LEFT && ZR_EXPORT_EYE_RIGHT == zr::EXPORT_EYE_RIGHT &&
+                  ZR_EXPORT_QUALITY == zr::EXPORT_QUALITY,
               "export flags");
+static_assert(sizeof(zr_face_quality) == 4 * zr::EXPORT_QUALITY_WORDS, "zr_face_quality words");
 
-int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_t slots, size_t num_landmarks,
-                          void *hip_stream) {
+static int multi_export(const zr_multi_export_args *a, const zr_face_quality *d_quality, zr_face_quality *d_out_quality,
+                        size_t n_streams, size_t slots, size_t num_landmarks, void *hip_stream) {
     return guarded([&]() -> int {
         if (!a) return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
         if (!a->d_nobjects || !a->d_src || !a->d_ids || !a->d_roi || !a->d_state || !a->d_landmarks || !a->d_count ||
@@ -1511,8 +1605,10 @@ int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_
         const int eyes = (a->d_eye_valid != nullptr) + (a->d_eye_diam != nullptr) + (a->d_eye_crop != nullptr) +
                          (a->d_eye_lm != nullptr) + (a->d_out_eye_valid != nullptr) + (a->d_out_eye_diam != nullptr) +
                          (a->d_out_eye_crop != nullptr) + (a->d_out_eye_lm != nullptr);
-        if ((pose != 0 && pose != 2) || (ident != 0 && ident != 4) || (eyes != 0 && eyes != 8))
-            return set_err(ZR_ERR_INVALID_ARGUMENT, "an optional group (pose, identity, eyes) is given in full or not at all");
+        const int qual = (d_quality != nullptr) + (d_out_quality != nullptr);
+        if ((pose != 0 && pose != 2) || (ident != 0 && ident != 4) || (eyes != 0 && eyes != 8) || (qual != 0 && qual != 2))
+            return set_err(ZR_ERR_INVALID_ARGUMENT,
+                           "an optional group (pose, identity, eyes, quality) is given in full or not at all");
         if (n_streams == 0) return set_err(ZR_ERR_INVALID_ARGUMENT, "no streams");
         if (slots == 0 || slots > 64) return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64");
         if (num_landmarks == 0 || num_landmarks > (1u << 20))
@@ -1533,6 +1629,7 @@ int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_
         p.eye_diam = reinterpret_cast<const uint32_t *>(a->d_eye_diam);
         p.eye_crop = reinterpret_cast<const uint32_t *>(a->d_eye_crop);
         p.eye_lm = reinterpret_cast<const uint32_t *>(a->d_eye_lm);
+        p.quality = reinterpret_cast<const uint32_t *>(d_quality);
         p.count = a->d_count;
         p.offsets = a->d_stream_offsets;
         p.header = reinterpret_cast<zr::ExportHeader *>(a->d_header);
@@ -1544,6 +1641,7 @@ int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_
         p.out_eye_diam = reinterpret_cast<uint32_t *>(a->d_out_eye_diam);
         p.out_eye_crop = reinterpret_cast<uint32_t *>(a->d_out_eye_crop);
         p.out_eye_lm = reinterpret_cast<uint32_t *>(a->d_out_eye_lm);
+        p.out_quality = reinterpret_cast<uint32_t *>(d_out_quality);
         p.S = (int)n_streams;
         p.K = (int)slots;
         p.L = (int)num_landmarks;
@@ -1555,6 +1653,17 @@ int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });
+}
+
+int zr_multi_export_async(const zr_multi_export_args *a, size_t n_streams, size_t slots, size_t num_landmarks,
+                          void *hip_stream) {
+    return multi_export(a, nullptr, nullptr, n_streams, slots, num_landmarks, hip_stream);
+}
+
+int zr_multi_export_quality_async(const zr_multi_export_args *a, const zr_face_quality *d_quality,
+                                  zr_face_quality *d_out_quality, size_t n_streams, size_t slots,
+                                  size_t num_landmarks, void *hip_stream) {
+    return multi_export(a, d_quality, d_out_quality, n_streams, slots, num_landmarks, hip_stream);
 }
 
 int zr_view_describe(const zr_view *views, size_t n, uint32_t frame, zr_view_desc *out) {

@@ -366,6 +366,41 @@ struct EyeCommitParams {
 };
 const char *launch_eye_commit(const EyeCommitParams &p, hipStream_t s);
 
+// The face quality gate of the recognition leg (kernels/quality.hip), between identity_select and
+// identity_compact: every due row's crop measured on the embedder's input grid (quality_math.h has
+// the arithmetic), rows that miss the embed tier taken off the due list.
+namespace quality {
+struct Record;
+}
+enum { QUALITY_FRAMES = 64 };  // frames a launch carries in its arguments, as EYE_CROP_FRAMES
+struct QualityParams {
+    FrameDesc frames[QUALITY_FRAMES];  // frames [base, base + QUALITY_FRAMES) of the caller's table
+    int base;                 // this launch measures the due rows of those frames; the launch with base 0
+                              // also those of no frame, and it alone copies the rows that are not due
+    int nframes;              // the whole table: a view whose frame index is >= nframes samples Color::NONE
+    const TrackState *state;  // [n]
+    const int32_t *src;       // [n] HandManageParams::src of the previous bookkeeping
+    const ViewDesc *views;    // [n] identity_select's crops (read for due rows only)
+    const uint32_t *pose;     // [n][EXPORT_POSE_WORDS] this step's zr_pose records, or null
+    const quality::Record *in;  // [n] the records the previous step wrote
+    quality::Record *out;     // [n] out, distinct from in
+    int32_t *due;             // [n] in / out: cleared for a row that misses the embed tier
+    unsigned long long *measured_total, *rejected_total;  // in / out, may be null
+    int n, K, ow, oh;
+    float embed[4], learn[4];  // the tiers' minima: size, inside, sharpness, frontal
+};
+const char *launch_quality_measure(const QualityParams &p, hipStream_t s);
+// due_of_learn[i] = due_of[i] where that is >= 0 and q[i] passed the learn tier, else -1;
+// *held_total += the rows with due_of[i] >= 0 that did not (may be null)
+struct QualityMaskParams {
+    const int32_t *due_of;       // [n]
+    const quality::Record *q;    // [n]
+    int32_t *due_of_learn;       // [n] out
+    unsigned long long *held_total;
+    int n;
+};
+const char *launch_quality_mask(const QualityMaskParams &p, hipStream_t s);
+
 // Every stream's objects that have a result as dense records (kernels/export.hip): slot j <
 // clamp(nobjects[s], 0, K) of stream s is exported iff r = src[s K + j] lies in [0, K); id, roi and
 // confidence come from slot j, everything else from slot r.  Layouts mirrored by zr_export_header /
@@ -383,8 +418,8 @@ struct ExportIdentity {
     float distance;
     uint32_t embeddings, flags;
 };
-enum { EXPORT_POSE = 1, EXPORT_IDENTITY = 2, EXPORT_EYE_LEFT = 4, EXPORT_EYE_RIGHT = 8 };
-enum { EXPORT_POSE_WORDS = 21, EXPORT_EYE_WORDS = 228 };  // zr_pose; 76 x 3 eye landmarks
+enum { EXPORT_POSE = 1, EXPORT_IDENTITY = 2, EXPORT_EYE_LEFT = 4, EXPORT_EYE_RIGHT = 8, EXPORT_QUALITY = 16 };
+enum { EXPORT_POSE_WORDS = 21, EXPORT_EYE_WORDS = 228, EXPORT_QUALITY_WORDS = 8 };  // zr_pose; 76 x 3 eye landmarks; zr_face_quality
 struct ExportParams {
     const int32_t *nobjects;     // [S]
     const int32_t *src;          // [S * K]
@@ -399,6 +434,7 @@ struct ExportParams {
     const uint32_t *eye_diam;    // [2 S K]
     const uint32_t *eye_crop;    // [2 S K][5]
     const uint32_t *eye_lm;      // [2 S K][228]
+    const uint32_t *quality;     // [S * K][8], null: no quality gate
     int32_t *count;              // out
     int32_t *offsets;            // [S + 1] out
     ExportHeader *header;        // [S * K] out: the first *count records, as every array below
@@ -408,6 +444,7 @@ struct ExportParams {
     uint32_t *out_emb;
     int32_t *out_eye_valid;
     uint32_t *out_eye_diam, *out_eye_crop, *out_eye_lm;
+    uint32_t *out_quality;
     int S, K, L;
     int vec4;                    // 3 L % 4 == 0 and lm, emb, eye_lm and their outputs 16-byte aligned
 };

@@ -20,7 +20,12 @@ device, and ``Gallery.rows()`` reads the enrolled people back.  Identities that 
 embeddings (what is matched, reported and enrolled), and ``set_gallery_refinement(gallery,
 max_samples=64, update_threshold=nan)`` moves a known object's gallery row towards each new embedding
 of it, on the device; ``refined_total()`` counts, ``Gallery.row_updates()`` / ``set_row_updates(counts)``
-save and restore the rows' sample counts beside ``rows()`` / ``add()``.
+save and restore the rows' sample counts beside ``rows()`` / ``add()``.  A face quality gate in front of
+it: ``set_identity_quality(embed_tier, learn_tier=None)`` with ``FaceQualityGate(min_size=-inf,
+min_inside=-inf, min_sharpness=-inf, min_frontal=-inf)`` tiers measures every due crop on the device; a
+crop below the embed tier is not embedded, one below the learn tier is neither enrolled nor refined from;
+``objects(s)[j]["quality"]`` and ``objects_packed()["quality"]`` carry the record while the gate is on,
+and ``face_quality(image, view, ow, oh, pose=None)`` is the same measurement of a host image.
 
 Tiled detection, for the small faces of a large frame: ``detection_tiles(width, height, cols, rows,
 overlap=0.25, include_full=True)`` gives the rects, ``TiledDetector(network, tiles)`` is the host
