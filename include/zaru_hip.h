@@ -562,6 +562,7 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
  *      the commit does; with refined rows: zr_identity_refine_async between commit and enrolment)
  *     (with the quality gate, below: zr_identity_quality_async between select and compact, and
  *      zr_identity_quality_mask_async after the commit, whose list refine and enrol then read)
+ *     (with aligned crops, further below: zr_identity_align_async right after select)
  * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
  * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
  * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
@@ -781,6 +782,67 @@ int zr_identity_quality_mask_async(size_t n, const int32_t *d_due_of, const zr_f
  * empty frame, ow or oh < 1, ow * oh > 16384, a NaN minimum. */
 int zr_face_quality_host(const zr_quality_cfg *cfg, const zr_frame *frame, const zr_view_desc *view,
                          const zr_pose *pose, zr_face_quality *out);
+
+/* ---- Aligned identity crops: a five-point similarity warp in the recognition leg -----------
+ * An opt-in stage between zr_identity_select_async and zr_identity_quality_async /
+ * zr_identity_compact_async: a due row's crop -- select's axis-aligned bounding crop -- is replaced
+ * by the crop that puts P points of the face where a template has them on the embedder's ow x oh
+ * input grid (the canonical five-point alignment of 112 x 112 face embedders), rotated by the roll
+ * of the head.  Everything downstream (the quality gate, the embedder, templates, enrolment,
+ * refinement) then sees the aligned crop.  All arithmetic is f32 without contraction, every operation
+ * rounded on its own, in this order (kernels/align_math.h, one source for host and device):
+ *     face points  q_p = the mean of the landmarks group[p][0..m): sx = ((0.f + x[i0]) + x[i1]) ...,
+ *                  q_p = (sx / (float)m, sy / (float)m); -1 ends a group
+ *     means        of tmpl and of q: in-order sums from 0, each / (float)P; t' and q' are centred
+ *     den          sum_p (t'x t'x then + t'y t'y), one product per step, p ascending
+ *     a, b         sum_p (t'x q'x then + t'y q'y) / den,  sum_p (t'x q'y then - t'y q'x) / den:
+ *                  the least-squares similarity without reflection, q ~ [[a, -b], [b, a]] t + T
+ *     scale, rad   sqrtf(a a + b b), atan2f(b, a) (glibc's, bit for bit)
+ *     crop         g = (ow 0.5f - mean_t.x, oh 0.5f - mean_t.y); centre c = mean_q + (a g.x - b g.y,
+ *                  b g.x + a g.y); the rotated rect {c, scale ow, scale oh, rad} as a view of the whole
+ *                  frame, as zr_identity_select_async builds its view
+ *     residual     sqrtf(sum_p |q'_p - M t'_p|^2 / (float)P) / scale, in grid pixels
+ * A row falls back -- its view stays exactly as select wrote it -- when scale, c.x or c.y is not
+ * finite or !(scale > 0) (ZR_ALIGN_FAIL_DEGENERATE), or !(residual <= max_residual)
+ * (ZR_ALIGN_FAIL_RESIDUAL; a NaN residual falls back).  NaNs in the record are the quiet NaN
+ * 0x7fc00000.  The defaults a caller picks are settings, not measurements. */
+typedef struct {
+    int32_t num_points;  /* P, 2..8 */
+    int32_t ow, oh;      /* the embedding network's input grid (112 x 112) */
+    float tmpl[8][2];    /* template points in that grid's local pixel coordinates */
+    int32_t group[8][4]; /* per template point 1..4 landmark indices whose mean is the face's point;
+                            -1 ends a group, the first entry is >= 0 */
+    float max_residual;  /* grid pixels; +inf: no limit */
+} zr_align_cfg;
+typedef struct {
+    float scale;    /* frame pixels per grid pixel */
+    float rad;      /* the crop's rotation */
+    float residual; /* grid pixels */
+    uint32_t flags; /* ZR_ALIGN_* */
+} zr_face_alignment; /* 16 bytes */
+#define ZR_ALIGN_ALIGNED 1u          /* the view is the aligned crop */
+#define ZR_ALIGN_FALLBACK 2u         /* the view is still select's bounding crop, because of: */
+#define ZR_ALIGN_FAIL_DEGENERATE 16u /* a non-finite or non-positive scale, a non-finite centre */
+#define ZR_ALIGN_FAIL_RESIDUAL 32u   /* the residual is above max_residual, or NaN */
+/* For a row with d_due[i] != 0: the fit on row i of d_landmarks (n x L x 3, frame px); when it
+ * aligns, d_views[i] is rewritten (the frame size from d_state[i], the frame index the one
+ * zr_identity_select_async left in d_views[i]); d_records[i] is written either way.  A row with
+ * d_due[i] == 0 has neither written.  d_totals (may be NULL): [0] += the rows aligned, [1] += the
+ * fallbacks (integer atomics).  One lane per row.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL required pointer, n == 0 or above
+ * 2^24, L < 1, num_points outside 2..8, ow or oh < 1, an empty group, an index >= L or < -1, a
+ * non-finite template coordinate, den == 0 or not finite (all template points coincide), a NaN
+ * max_residual. */
+int zr_identity_align_async(const zr_align_cfg *cfg, const zr_track_state *d_state, size_t n,
+                            const float *d_landmarks, size_t num_landmarks, const int32_t *d_due,
+                            zr_view_desc *d_views, zr_face_alignment *d_records, uint64_t *d_totals,
+                            void *hip_stream);
+/* The same fit on the host, for one face: `landmarks` are L points of `stride` >= 2 floats (x, y
+ * first).  *out is the record; *view the aligned crop as a view of frame `frame` (frame_w x frame_h),
+ * the same bits as the device's, and not written on a fallback.  Refused as above, and: stride < 2. */
+int zr_face_align_host(const zr_align_cfg *cfg, const float *landmarks, size_t num_landmarks, size_t stride,
+                       uint32_t frame_w, uint32_t frame_h, uint32_t frame, zr_view_desc *view,
+                       zr_face_alignment *out);
 
 /* ---- Iris and eye-contour refinement of the tracked faces inside the multi-object loop -----
  * The reference has the two halves of the cascade -- FaceMeshV1::left_eye / right_eye

@@ -122,6 +122,35 @@ QUALITY_MEASURED, QUALITY_EMBED, QUALITY_LEARN = 1, 2, 4
 QUALITY_FAIL_SIZE, QUALITY_FAIL_INSIDE, QUALITY_FAIL_SHARPNESS, QUALITY_FAIL_FRONTAL = 16, 32, 64, 128
 
 
+class AlignCfg(C.Structure):
+    """zr_align_cfg: the aligned identity crop's template, landmark groups (-1 ends a group) and limit."""
+    _fields_ = [("num_points", C.c_int32), ("ow", C.c_int32), ("oh", C.c_int32), ("tmpl", C.c_float * 2 * 8),
+                ("group", C.c_int32 * 4 * 8), ("max_residual", C.c_float)]
+
+    @classmethod
+    def make(cls, template, groups, ow=112, oh=112, max_residual=float("inf")):
+        """template: P points (x, y); groups: P lists of 1..4 landmark indices.  Nothing is checked
+        here: the entry points refuse what they refuse."""
+        c = cls(len(template), ow, oh)
+        c.max_residual = max_residual
+        for p in range(8):
+            for j in range(4):
+                c.group[p][j] = -1
+        for p, (t, g) in enumerate(zip(template[:8], groups[:8])):
+            c.tmpl[p][0], c.tmpl[p][1] = float(t[0]), float(t[1])
+            for j, idx in enumerate(list(g)[:4]):
+                c.group[p][j] = int(idx)
+        return c
+
+
+class FaceAlignment(C.Structure):
+    """zr_face_alignment: the record of one fit (16 bytes)."""
+    _fields_ = [("scale", C.c_float), ("rad", C.c_float), ("residual", C.c_float), ("flags", C.c_uint32)]
+
+
+ALIGN_ALIGNED, ALIGN_FALLBACK, ALIGN_FAIL_DEGENERATE, ALIGN_FAIL_RESIDUAL = 1, 2, 16, 32
+
+
 class ExportHeader(C.Structure):
     """zr_export_header: the fixed part of one record of zr_multi_export_async (48 bytes)."""
     _fields_ = [("id", C.c_uint64), ("stream", C.c_int32), ("slot", C.c_int32), ("roi", C.c_float * 5),
@@ -210,6 +239,8 @@ SIGNATURES = [
     ("zr_identity_quality_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_quality_mask_async", _I, [_SZ, _P, _P, _P, _P, _P]),
     ("zr_face_quality_host", _I, [_P, _P, _P, _P, _P]),
+    ("zr_identity_align_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
+    ("zr_face_align_host", _I, [_P, _P, _SZ, _SZ, _U32, _U32, _U32, _P, _P]),
     ("zr_embed_match_count_async", _I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     ("zr_eye_select_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     ("zr_eye_crop_async", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _U32, _U32, _P]),

@@ -194,6 +194,54 @@ PYBIND11_MODULE(_zaru_host, m) {
         return quality_dict(q);
     }, py::arg("image"), py::arg("view"), py::arg("ow"), py::arg("oh"), py::arg("pose") = py::none(),
        py::arg("embed_tier") = py::none(), py::arg("learn_tier") = py::none());
+    // the settings of the aligned identity crop (zr_align_cfg): `template` 2..8 points (x, y) on the ow x oh
+    // grid, `groups` one list of 1..4 landmark indices per point (settings, not measurements)
+    py::class_<FaceAlignment>(m, "FaceAlignment")
+        .def(py::init([](const std::vector<std::array<float, 2>> &tmpl, const std::vector<std::vector<int32_t>> &groups,
+                         int ow, int oh, float max_residual) {
+                 if (tmpl.size() < 2 || tmpl.size() > 8 || groups.size() != tmpl.size())
+                     throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "2..8 template points, and one landmark group for each");
+                 FaceAlignment a;
+                 a.cfg.num_points = (int32_t)tmpl.size();
+                 a.cfg.ow = ow;
+                 a.cfg.oh = oh;
+                 a.cfg.max_residual = max_residual;
+                 for (int p = 0; p < 8; p++)
+                     for (int j = 0; j < 4; j++) a.cfg.group[p][j] = -1;
+                 for (size_t p = 0; p < tmpl.size(); p++) {
+                     a.cfg.tmpl[p][0] = tmpl[p][0];
+                     a.cfg.tmpl[p][1] = tmpl[p][1];
+                     if (groups[p].empty() || groups[p].size() > 4)
+                         throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "a landmark group holds 1..4 indices");
+                     for (size_t j = 0; j < groups[p].size(); j++) {
+                         // (-1 would end the group early: an index is >= 0 here, or refused below as < -1)
+                         if (groups[p][j] < 0) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "a negative landmark index");
+                         a.cfg.group[p][j] = groups[p][j];
+                     }
+                 }
+                 return a;
+             }),
+             py::arg("template"), py::arg("groups"), py::arg("ow") = 112, py::arg("oh") = 112,
+             py::arg("max_residual") = INFINITY)
+        .def_static("facemesh_five_point", &FaceAlignment::facemesh_five_point)
+        .def_property_readonly("num_points", [](const FaceAlignment &a) { return a.cfg.num_points; })
+        .def_property_readonly("ow", [](const FaceAlignment &a) { return a.cfg.ow; })
+        .def_property_readonly("oh", [](const FaceAlignment &a) { return a.cfg.oh; })
+        .def_property("max_residual", [](const FaceAlignment &a) { return a.cfg.max_residual; },
+                      [](FaceAlignment &a, float v) { a.cfg.max_residual = v; })
+        .def_property_readonly("template", [](const FaceAlignment &a) {
+            return f32_array(&a.cfg.tmpl[0][0], {(py::ssize_t)a.cfg.num_points, (py::ssize_t)2});
+        })
+        .def_property_readonly("groups", [](const FaceAlignment &a) {
+            std::vector<std::vector<int32_t>> g((size_t)a.cfg.num_points);
+            for (int p = 0; p < a.cfg.num_points; p++)
+                for (int j = 0; j < 4 && a.cfg.group[p][j] >= 0; j++) g[p].push_back(a.cfg.group[p][j]);
+            return g;
+        })
+        // the zr_align_cfg itself, for zaru_amd._lib's ctypes entry points
+        .def("cfg_bytes", [](const FaceAlignment &a) {
+            return py::bytes(reinterpret_cast<const char *>(&a.cfg), sizeof(a.cfg));
+        });
 
     py::class_<Rect>(m, "Rect")
         .def_static("from_center", &Rect::from_center)
@@ -628,6 +676,15 @@ PYBIND11_MODULE(_zaru_host, m) {
             const zr_quality_tier l = learn.cast<zr_quality_tier>();
             t.set_identity_quality(&e, &l);
         }, py::arg("embed_tier"), py::arg("learn_tier") = py::none())
+        // aligned identity crops: a FaceAlignment; None: off
+        .def("set_identity_alignment", [](DeviceMultiTracker &t, const py::object &alignment) {
+            if (alignment.is_none()) return t.set_identity_alignment(nullptr);
+            const FaceAlignment a = alignment.cast<FaceAlignment>();
+            t.set_identity_alignment(&a);
+        }, py::arg("alignment"))
+        .def("identity_alignment", &DeviceMultiTracker::identity_alignment)
+        .def("aligned_total", &DeviceMultiTracker::aligned_total)
+        .def("align_fallback_total", &DeviceMultiTracker::align_fallback_total)
         .def("identity_quality", &DeviceMultiTracker::identity_quality)
         .def("quality_measured_total", &DeviceMultiTracker::quality_measured_total)
         .def("quality_rejected_total", &DeviceMultiTracker::quality_rejected_total)
@@ -1087,6 +1144,14 @@ PYBIND11_MODULE(_zaru_host, m) {
                 std::memcpy(a.mutable_data() + i * EMBEDDING_DIM, v[i].v.data(), EMBEDDING_DIM * sizeof(float));
             return a;
         })
+        .def("embed_views", [](const FaceEmbedder &e, py::array_t<uint8_t, py::array::c_style> img,
+                               const std::vector<ViewData> &views) {
+            const auto v = e.embed_views(host_image(img), views);
+            py::array_t<float> a({(py::ssize_t)v.size(), (py::ssize_t)EMBEDDING_DIM});
+            for (size_t i = 0; i < v.size(); i++)
+                std::memcpy(a.mutable_data() + i * EMBEDDING_DIM, v[i].v.data(), EMBEDDING_DIM * sizeof(float));
+            return a;
+        })
         .def("embed_first_face", [embedding_array](const FaceEmbedder &e, Detector &d,
                                                    py::array_t<uint8_t, py::array::c_style> img) -> py::object {
             Embedding out;
@@ -1102,6 +1167,21 @@ PYBIND11_MODULE(_zaru_host, m) {
                                   grow, (size_t)landmarks.shape(1));
     }, py::arg("landmarks"), py::arg("image_w"), py::arg("image_h"), py::arg("aspect_w"), py::arg("aspect_h"),
           py::arg("grow") = FaceEmbedder::CROP_GROW);
+    // (ViewData or None, the fit's record); None: the fit fell back, crop with landmark_crop_view
+    m.def("aligned_crop_view", [](py::array_t<float, py::array::c_style> landmarks, uint32_t image_w, uint32_t image_h,
+                                  const FaceAlignment &alignment) {
+        if (landmarks.ndim() != 2 || landmarks.shape(0) < 1 || landmarks.shape(1) < 2)
+            throw ZaruError(ZR_ERR_SHAPE, "landmarks must be [L >= 1][C >= 2]");
+        zr_face_alignment r{};
+        const auto v = aligned_crop_view(landmarks.data(), (size_t)landmarks.shape(0), image_w, image_h, alignment,
+                                         (size_t)landmarks.shape(1), &r);
+        py::dict d;
+        d["scale"] = r.scale;
+        d["angle"] = r.rad;
+        d["residual"] = r.residual;
+        d["flags"] = r.flags;
+        return py::make_tuple(v ? py::cast(*v) : py::object(py::none()), d);
+    }, py::arg("landmarks"), py::arg("image_w"), py::arg("image_h"), py::arg("alignment"));
     // ---- iris and eye-contour refinement of a face mesh (face/eye.rs + mediapipe.rs:162-192)
     auto face_mesh_arg = [](const py::array_t<float, py::array::c_style | py::array::forcecast> &lm) {
         if (lm.ndim() != 2 || lm.shape(0) < 387 || lm.shape(1) != 3)

@@ -163,6 +163,10 @@ void DeviceMultiTracker::set_identity_quality(const zr_quality_tier *embed, cons
     identity_.set_quality(ctx(), embed, learn);
 }
 
+void DeviceMultiTracker::set_identity_alignment(const FaceAlignment *alignment) {
+    identity_.set_alignment(ctx(), alignment);
+}
+
 void DeviceMultiTracker::set_eye_crop_grow(float g) {
     if (!(g >= 0.f)) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "eye crop grow factor must be >= 0");
     eyes_.cfg.crop_grow = g;
@@ -328,6 +332,8 @@ uint64_t DeviceMultiTracker::refined_total() { return read_u64(identity_.refine_
 uint64_t DeviceMultiTracker::quality_measured_total() { return read_u64(identity_.quality.counts, 0); }
 uint64_t DeviceMultiTracker::quality_rejected_total() { return read_u64(identity_.quality.counts, 1); }
 uint64_t DeviceMultiTracker::quality_held_back_total() { return read_u64(identity_.quality.counts, 2); }
+uint64_t DeviceMultiTracker::aligned_total() { return read_u64(identity_.align.counts, 0); }
+uint64_t DeviceMultiTracker::align_fallback_total() { return read_u64(identity_.align.counts, 1); }
 uint64_t DeviceMultiTracker::eye_images() { return read_u64(eyes_.total); }
 
 std::vector<DeviceMultiTracker::ObjectData> DeviceMultiTracker::objects(size_t s) {

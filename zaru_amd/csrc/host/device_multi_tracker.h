@@ -142,6 +142,17 @@ class DeviceMultiTracker {
     uint64_t quality_measured_total();   // crops measured, summed (0 before set_identity_quality)
     uint64_t quality_rejected_total();   // of those, the ones that missed the embed tier
     uint64_t quality_held_back_total();  // objects embedded but kept out of enrolment and refinement
+    // Aligned identity crops (MultiAlign in multi_stages.h; zr_identity_align_async in
+    // include/zaru_hip.h has the arithmetic): every due object's crop becomes the similarity crop that
+    // puts its face points on `alignment`'s template -- rotated by the roll of the head -- instead of
+    // the landmarks' axis-aligned bounding crop; an object whose fit falls back (degenerate, or past
+    // max_residual) keeps the bounding crop.  The quality gate, the embedder and everything that
+    // learns see the aligned crop.  The grid must be the embedder's input.  Needs recognition; every
+    // set_recognition turns it off; nullptr turns it off, and the next step crops as before.
+    void set_identity_alignment(const FaceAlignment *alignment);
+    bool identity_alignment() const { return identity_.align.on(); }
+    uint64_t aligned_total();         // due crops aligned, summed (0 before set_identity_alignment)
+    uint64_t align_fallback_total();  // due crops that kept the bounding crop while alignment was on
     // Eye refinement of every tracked face, every step (default off).  Refused unless the
     // landmarker is FaceMesh V1 or V2.  The first call loads the eye network and allocates; off: a
     // step enqueues what it did without, and objects() reports no eyes.

@@ -59,6 +59,7 @@ void MultiIdentity::set(const MultiCtx &c, const std::vector<uint8_t> &model, co
     enrol = refine = nullptr;  // enrolment, refinement and smoothing belong to the gallery they were set for
     template_cap = 1;
     quality.enabled = quality.ran = false;  // and the quality gate to the embedder
+    align.enabled = false;                  // as the alignment's grid does
     embedder = std::move(emb);
     gallery = embedder ? g : nullptr;
     ran = false;
@@ -164,6 +165,31 @@ void MultiIdentity::set_quality(const MultiCtx &c, const zr_quality_tier *embed,
     quality.ran = false;
 }
 
+void MultiIdentity::set_alignment(const MultiCtx &c, const FaceAlignment *a) {
+    if (!a) {
+        c.synchronize();
+        align.enabled = false;
+        return;
+    }
+    if (!on()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "aligned crops need recognition (set_recognition)");
+    const Cnn &ec = embedder->cnn();
+    if ((uint32_t)a->cfg.ow != ec.input_width() || (uint32_t)a->cfg.oh != ec.input_height())
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the alignment's grid must be the embedding network's input");
+    {  // what the launches would refuse is refused here, before anything changes
+        const std::vector<float> lm((size_t)c.num_landmarks * 3, 0.f);
+        zr_view_desc v{};
+        zr_face_alignment r{};
+        check(zr_face_align_host(&a->cfg, lm.data(), (size_t)c.num_landmarks, 3, 1, 1, 0, &v, &r));
+    }
+    c.synchronize();  // the last step's launches still write the records
+    align.recs.resize(c.rows());
+    check(zr_memset_async(align.recs.ptr, 0, c.rows() * sizeof(zr_face_alignment), c.stream));
+    zero_once(align.counts, 2, c.stream);
+    check(zr_stream_synchronize(c.stream));
+    align.cfg = a->cfg;
+    align.enabled = true;
+}
+
 void MultiIdentity::frame_size(const MultiCtx &c, const zr_view_desc &det_tmpl) {
     const auto rows = upload_frame_views(due_views.ptr, &det_tmpl, 1, c.rows(), (size_t)c.slots, c.stream);
     check(zr_stream_synchronize(c.stream));
@@ -177,6 +203,9 @@ void MultiIdentity::enqueue(const MultiCtx &c, const std::vector<zr_frame> &fram
     const int in = flipped ? 1 : 0, o = 1 - in;
     check(zr_identity_select_async(&cfg, d_state, nv, d_landmarks, d_src, now_ms, states[in].ptr, embs[in].ptr,
                                    states[o].ptr, embs[o].ptr, due.ptr, views.ptr, stream));
+    if (align.on())  // the due rows' bounding crops replaced by the aligned ones, where the fit holds
+        check(zr_identity_align_async(&align.cfg, d_state, nv, d_landmarks, (size_t)c.num_landmarks, due.ptr, views.ptr,
+                                      align.recs.ptr, align.counts.ptr, stream));
     if (quality.on())  // the due rows measured; those that miss the embed tier leave the due list
         check(zr_identity_quality_async(&quality.cfg, frames.data(), c.streams, d_state, nv, d_src, views.ptr, d_pose,
                                         quality.recs[in].ptr, quality.recs[o].ptr, due.ptr, quality.counts.ptr,

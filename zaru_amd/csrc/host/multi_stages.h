@@ -59,6 +59,22 @@ struct MultiQuality {
     bool needs_pose() const { return cfg.embed.min_frontal > -INFINITY || cfg.learn.min_frontal > -INFINITY; }
 };
 
+// Aligned identity crops (opt-in, MultiIdentity::set_alignment; zr_identity_align_async in
+// include/zaru_hip.h has the arithmetic): a member of MultiIdentity, whose enqueue() runs it between
+// a. and the quality gate.  Every due object's bounding crop is replaced by the similarity crop that
+// puts its face points where the template has them on the embedder's input grid; an object whose fit
+// falls back keeps the bounding crop.  Everything after it -- the gate, the embedder, templates,
+// enrolment, refinement -- sees the aligned crop: the gate's size is scale * min(ow, oh), its inside
+// fraction and sharpness are measured on the rotated grid.  The records are per slot and of this step
+// only (they do not follow the object).  Off, nothing of this is enqueued or allocated.
+struct MultiAlign {
+    bool enabled = false;
+    zr_align_cfg cfg{};
+    DeviceArray<zr_face_alignment> recs;  // [rows] written for the rows due at the last step
+    DeviceArray<uint64_t> counts;         // [0] aligned, [1] fallbacks
+    bool on() const { return enabled; }
+};
+
 // Recognition (opt-in, set): every object carries an identity -- the gallery row it matched, the
 // distance, how often it was embedded, its last embedding and when it is due again -- that follows
 // it between slots through the bookkeeping's `src`, as the filter state does.  Between the loop's
@@ -103,6 +119,7 @@ struct MultiIdentity {
     float refine_threshold = NAN;        // NaN: the identity threshold at each step
     DeviceArray<uint64_t> refine_total;  // [0] contributions applied
     MultiQuality quality;                // the quality gate (off by default)
+    MultiAlign align;                    // aligned crops (off by default)
 
     MultiIdentity();
     bool on() const { return embedder != nullptr; }
@@ -117,6 +134,8 @@ struct MultiIdentity {
     void set_refinement(const MultiCtx &c, Gallery *g, uint32_t max_samples, float update_threshold);
     // DeviceMultiTracker::set_identity_quality; embed == nullptr: off.  Resets every object's record.
     void set_quality(const MultiCtx &c, const zr_quality_tier *embed, const zr_quality_tier *learn);
+    // DeviceMultiTracker::set_identity_alignment; nullptr: off
+    void set_alignment(const MultiCtx &c, const FaceAlignment *a);
     bool quality_result() const { return on() && quality.on() && quality.ran; }
     const DeviceArray<zr_face_quality> &quality_state() const { return quality.recs[flipped ? 1 : 0]; }
     // a valid view in every entry of the packed crop table, as the loop's frame_size() does for its own

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <limits>
 
+#include "../kernels/align_math.h"
+
 namespace zh {
 
 // (compiled with -ffp-contract=off: d * d and the add round separately, as the Rust does)
@@ -43,6 +45,15 @@ std::vector<Embedding> FaceEmbedder::embed(const Image &img, const std::vector<R
     return out;
 }
 
+std::vector<Embedding> FaceEmbedder::embed_views(const Image &img, const std::vector<ViewData> &views) const {
+    std::vector<Embedding> out(views.size());
+    if (views.empty()) return out;
+    const auto outs = cnn_->estimate(img, views);
+    for (size_t i = 0; i < views.size(); i++)
+        std::memcpy(out[i].v.data(), outs[0].data() + i * EMBEDDING_DIM, EMBEDDING_DIM * sizeof(float));
+    return out;
+}
+
 bool FaceEmbedder::embed_first_face(Detector &detector, const Image &img, Embedding &out) const {
     const std::vector<Detection> &dets = detector.detect(img);
     if (dets.empty()) return false;
@@ -60,6 +71,41 @@ ViewData landmark_crop_view(const float *landmarks, size_t L, uint32_t image_w, 
     Rect::bounding(pts.data(), L, box);
     const Rect r = box.grow_rel(grow).grow_to_fit_aspect(AspectRatio{aspect_w, aspect_h});
     return ViewData::full(image_w, image_h).view(RotatedRect(r, 0.f));
+}
+
+FaceAlignment FaceAlignment::facemesh_five_point() {
+    FaceAlignment a;
+    a.cfg.num_points = 5;
+    a.cfg.ow = a.cfg.oh = 112;
+    const float t[5][2] = {{38.2946f, 51.6963f}, {73.5318f, 51.5014f}, {56.0252f, 71.7366f},
+                           {41.5493f, 92.3655f}, {70.7299f, 92.2041f}};
+    const int32_t g[5][4] = {{33, 133, -1, -1}, {362, 263, -1, -1}, {1, -1, -1, -1}, {61, -1, -1, -1},
+                             {291, -1, -1, -1}};
+    for (int p = 0; p < 8; p++)
+        for (int j = 0; j < 4; j++) a.cfg.group[p][j] = -1;
+    for (int p = 0; p < 5; p++) {
+        a.cfg.tmpl[p][0] = t[p][0];
+        a.cfg.tmpl[p][1] = t[p][1];
+        for (int j = 0; j < 4; j++) a.cfg.group[p][j] = g[p][j];
+    }
+    a.cfg.max_residual = std::numeric_limits<float>::infinity();
+    return a;
+}
+
+std::optional<ViewData> aligned_crop_view(const float *landmarks, size_t L, uint32_t image_w, uint32_t image_h,
+                                          const FaceAlignment &alignment, size_t stride, zr_face_alignment *record) {
+    // the refusals are the C entry point's; its view is not used: the ViewData is made from the crop
+    zr_view_desc unused{};
+    zr_face_alignment rec{};
+    check(zr_face_align_host(&alignment.cfg, landmarks, L, stride, image_w, image_h, 0, &unused, &rec));
+    if (record) *record = rec;
+    if (!(rec.flags & ZR_ALIGN_ALIGNED)) return std::nullopt;
+    zr::align::Cfg c;
+    std::memcpy(&c, &alignment.cfg, sizeof c);
+    zr::align::Crop k;
+    zr::align::Record r;
+    zr::align::fit(c, landmarks, (int)stride, k, r);
+    return ViewData::full(image_w, image_h).view(RotatedRect(Rect::from_center(k.cx, k.cy, k.w, k.h), k.rad));
 }
 
 // ------------------------------------------------------------------ Gallery

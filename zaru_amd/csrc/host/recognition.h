@@ -11,6 +11,7 @@
 #include <array>
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <vector>
 
 #include "detection.h"
@@ -36,6 +37,8 @@ class FaceEmbedder {
     // whole image (lines 82-91; a Rect is a rotation-0 view, image/mod.rs:151-156)
     ViewData crop_view(uint32_t image_w, uint32_t image_h, const Rect &rect) const;
     std::vector<Embedding> embed(const Image &img, const std::vector<Rect> &rects) const;
+    // embed on views the caller made (crop_view, landmark_crop_view, aligned_crop_view): rotated crops
+    std::vector<Embedding> embed_views(const Image &img, const std::vector<ViewData> &views) const;
     // the example's loop body for one image: the first detection (NMS order); false when none
     bool embed_first_face(Detector &detector, const Image &img, Embedding &out) const;
 
@@ -51,6 +54,28 @@ class FaceEmbedder {
 // device (kernels/identity.hip); needs no device.  Throws for L == 0, stride < 2 or a zero aspect.
 ViewData landmark_crop_view(const float *landmarks, size_t L, uint32_t image_w, uint32_t image_h, uint32_t aspect_w,
                             uint32_t aspect_h, float grow = FaceEmbedder::CROP_GROW, size_t stride = 3);
+
+// The aligned crop of a tracked face (zr_identity_align_async in include/zaru_hip.h has the
+// arithmetic; kernels/align_math.h is its one source): the least-squares similarity that maps a
+// template of 2..8 points on the embedder's input grid onto the means of landmark groups, as a
+// rotated view of the whole image.  The settings are a zr_align_cfg.
+struct FaceAlignment {
+    zr_align_cfg cfg{};
+    // The widely published five-point template of 112 x 112 face embedders (eye centres, nose tip,
+    // mouth corners) on FaceMesh's points: {33, 133}, {362, 263}, {1}, {61}, {291} -- the image-left eye
+    // first, so that q0.x < q1.x for an upright face in a frame that is not mirrored.  max_residual
+    // +inf.  Settings, not measurements: whether a given embedder was trained on this template is the
+    // caller's knowledge.
+    static FaceAlignment facemesh_five_point();
+};
+// The aligned crop of `landmarks` (L points of `stride` floats, x and y first; frame px) in an
+// image_w x image_h image, or nothing when the fit falls back (the caller then uses
+// landmark_crop_view); *record (may be null) gets the fit's record either way.  zr_view_describe of
+// the view is bit for bit what zr_face_align_host and the device write.  Needs no device.  Throws what
+// zr_face_align_host refuses.
+std::optional<ViewData> aligned_crop_view(const float *landmarks, size_t L, uint32_t image_w, uint32_t image_h,
+                                          const FaceAlignment &alignment, size_t stride = 3,
+                                          zr_face_alignment *record = nullptr);
 
 class Gallery {
   public:

@@ -18,6 +18,7 @@
 #include "onnx_model.h"
 #include "plan.h"
 #include "zr_track.h"
+#include "zr_align.h"
 #include "../kernels/procrustes_math.h"
 #include "../kernels/eye_math.h"
 #include "../kernels/quality_math.h"
@@ -40,6 +41,7 @@ int set_err(int code, const std::string &msg) noexcept {
 // (runtime/jpeg.cpp)
 namespace zr_internal {
 int set_error(int code, const std::string &msg) { return set_err(code, msg); }
+int align_check(const zr_align_cfg *cfg, size_t num_landmarks);  // host/align.cpp, shared with zr_face_align_host
 }  // namespace zr_internal
 
 namespace {
@@ -1466,6 +1468,35 @@ int zr_identity_quality_mask_async(size_t n, const int32_t *d_due_of, const zr_f
         p.held_total = reinterpret_cast<unsigned long long *>(d_held_total);
         p.n = (int)n;
         zr::launch_quality_mask(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
+// ---- the aligned identity crop of the recognition leg (kernels/align.hip)
+static_assert(sizeof(zr_align_cfg) == sizeof(zr::align::Cfg) && sizeof(zr_face_alignment) == sizeof(zr::align::Record),
+              "alignment layouts");
+
+int zr_identity_align_async(const zr_align_cfg *cfg, const zr_track_state *d_state, size_t n,
+                            const float *d_landmarks, size_t num_landmarks, const int32_t *d_due,
+                            zr_view_desc *d_views, zr_face_alignment *d_records, uint64_t *d_totals,
+                            void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!cfg || !d_state || !d_landmarks || !d_due || !d_views || !d_records)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+        if (int rc = zr_internal::align_check(cfg, num_landmarks)) return rc;
+        zr::AlignParams p{};
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.lm = d_landmarks;
+        p.due = d_due;
+        p.views = reinterpret_cast<zr::ViewDesc *>(d_views);
+        p.recs = reinterpret_cast<zr::align::Record *>(d_records);
+        p.totals = reinterpret_cast<unsigned long long *>(d_totals);
+        p.n = (int)n;
+        p.L = (int)num_landmarks;
+        std::memcpy(&p.cfg, cfg, sizeof p.cfg);
+        zr::launch_identity_align(p, (hipStream_t)hip_stream);
         HIP_TRY(hipGetLastError());
         return ZR_OK;
     });

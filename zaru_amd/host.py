@@ -26,6 +26,11 @@ min_inside=-inf, min_sharpness=-inf, min_frontal=-inf)`` tiers measures every du
 crop below the embed tier is not embedded, one below the learn tier is neither enrolled nor refined from;
 ``objects(s)[j]["quality"]`` and ``objects_packed()["quality"]`` carry the record while the gate is on,
 and ``face_quality(image, view, ow, oh, pose=None)`` is the same measurement of a host image.
+Aligned crops: ``set_identity_alignment(FaceAlignment.facemesh_five_point())`` (or ``FaceAlignment(template,
+groups, ow=112, oh=112, max_residual=inf)``; ``None``: off) replaces every due object's bounding crop by the
+five-point similarity crop, rotated by the roll of the head; ``aligned_total()`` / ``align_fallback_total()``
+count, ``aligned_crop_view(landmarks, image_w, image_h, alignment)`` gives ``(ViewData | None, record)`` on
+the host and ``FaceEmbedder.embed_views(image, views)`` embeds such views.
 
 Tiled detection, for the small faces of a large frame: ``detection_tiles(width, height, cols, rows,
 overlap=0.25, include_full=True)`` gives the rects, ``TiledDetector(network, tiles)`` is the host
