@@ -563,6 +563,7 @@ int zr_track_reseed_best_async(const int32_t *d_count, const float *d_dets, size
  *     (with the quality gate, below: zr_identity_quality_async between select and compact, and
  *      zr_identity_quality_mask_async after the commit, whose list refine and enrol then read)
  *     (with aligned crops, further below: zr_identity_align_async right after select)
+ *     (with merging of duplicate rows: zr_identity_link_async last of all, after the enrolment)
  * The n = streams x slots rows are the tracker's slots, stream s owning rows [s * slots, s * slots +
  * slots).  An identity is one zr_identity_state and one row of 128 floats per slot, in two buffers
  * each: a step reads `in`, writes `out`, and the caller swaps them afterwards.  The crop is taken
@@ -699,6 +700,55 @@ int zr_identity_refine_async(const zr_identity_cfg *cfg, size_t n, const int32_t
                              uint32_t *d_updates, const int32_t *d_count, size_t capacity, size_t dim,
                              uint32_t max_samples, float update_threshold, uint64_t *d_refined_total,
                              void *hip_stream);
+/* Merging duplicate gallery rows from track evidence, issued last in the identity leg: after
+ * zr_identity_commit_async, zr_identity_quality_mask_async, zr_identity_refine_async and
+ * zr_identity_enrol_async.  Rows are neither removed nor moved: every gallery row has one link
+ * record, whose alias is the canonical row of the row's person.  A merged person keeps all rows as
+ * templates (the nearest-row match serves them as it is), and every row the loop reports is the
+ * canonical one.  The table is flat: d_links[d_links[r].alias].alias == d_links[r].alias.
+ * Invariant: a row at or past the gallery's count holds its default record, so appending a row (by
+ * add() or by enrolment) needs no write here. */
+typedef struct {
+    int32_t alias;     /* canonical row of this row's person; alias <= own row; alias of a canonical row is itself */
+    int32_t partner;   /* on a canonical row: the lower canonical row it is suspected to be, -1: none */
+    uint32_t seen;     /* observations of (partner, this row) so far */
+    uint32_t reserved; /* 0 */
+} zr_gallery_link;     /* 16 bytes; the default record of row r is {r, -1, 0, 0} */
+/* G = clamp(*d_count, 0, capacity); alias(r) = d_links[r].alias, read as r when it lies outside
+ * [0, r] (no index leaves the table, whatever it holds).  d_in / d_out are the identity states the
+ * step read and wrote (select's gather source and the committed states), d_src and d_state as for
+ * zr_identity_select_async, d_due_of the list refine and enrol were handed.
+ * Pass 1, skipped when min_observations == 0 (a tracker that only reads a gallery another one
+ * merges).  The rows i = 0 .. n-1 are taken in row order (stream-major, then slot order) by one
+ * workgroup, so the outcome never depends on scheduling:
+ *   1. row i is eligible when d_due_of[i] lies in [0, n), d_state[i].tracked != 0 and d_src[i] lies in
+ *      [0, slots) (a new object has no history);
+ *   2. with carried = d_in[(i / slots) * slots + d_src[i]], p = carried.row, dp = carried.distance, b =
+ *      d_out[i].row, db = d_out[i].distance, the row is evidence when 0 <= p < G, 0 <= b < G, dp <=
+ *      link_threshold and db <= link_threshold (NaN: never; +inf: every known pair), and alias(p) !=
+ *      alias(b) with the aliases as they are at this moment, after the merges this call has made.
+ *      lo = the smaller, hi = the larger of the two canonical rows;
+ *   3. veto: if any other row j of the same stream has d_state[j].tracked != 0, 0 <= d_out[j].row < G
+ *      and alias(d_out[j].row) equal to lo or hi, both people are in this frame: d_links[hi] = {hi, -1,
+ *      0, 0}, one veto is counted, and there is no observation;
+ *   4. otherwise one observation is counted; seen = d_links[hi].seen + 1 (as uint32) if
+ *      d_links[hi].partner == lo, else 1.  If seen >= min_observations the rows merge: d_links[r].alias
+ *      = lo for every r < G with alias(r) == hi, d_links[hi].partner = -1, d_links[hi].seen = 0, one merge
+ *      is counted.  Otherwise d_links[hi].partner = lo and d_links[hi].seen = seen.
+ * Pending records that went stale (on a row that stopped being canonical, or whose partner did)
+ * are not fixed up: they mismatch at 4. and are replaced.
+ * Pass 2, always, one thread per row: where 0 <= d_out[i].row < G, d_out[i].row = alias(d_out[i].row).
+ * Nothing else of the state moves: the distance stays the one to the person's nearest template.
+ * d_counts[0..2] += merges, vetoes, observations (d_counts may be NULL).  Nothing eligible and every
+ * reported row canonical: no byte of d_links, d_out or d_counts is written.
+ * Refused with ZR_ERR_INVALID_ARGUMENT, nothing launched: a NULL pointer other than d_counts, n == 0
+ * or above 2^24, slots outside 1..64, n not a multiple of slots, capacity == 0 or above 2^31 - 1,
+ * d_in == d_out.  The threshold and min_observations are settings, not errors. */
+int zr_identity_link_async(const zr_identity_cfg *cfg, const zr_track_state *d_state, size_t n,
+                           const int32_t *d_src, const int32_t *d_due_of, const zr_identity_state *d_in,
+                           zr_identity_state *d_out, zr_gallery_link *d_links, const int32_t *d_count,
+                           size_t capacity, uint32_t min_observations, float link_threshold, uint64_t *d_counts,
+                           void *hip_stream);
 
 /* ---- Face quality gate of the recognition leg ------------------------------------------------
  * An opt-in stage between zr_identity_select_async and zr_identity_compact_async: what the

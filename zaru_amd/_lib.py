@@ -89,6 +89,12 @@ class IdentityState(C.Structure):
                 ("next_ms", C.c_double)]
 
 
+class GalleryLink(C.Structure):
+    """zr_gallery_link: one gallery row's link record (16 bytes).  The default record of row r is
+    {r, -1, 0, 0}."""
+    _fields_ = [("alias", C.c_int32), ("partner", C.c_int32), ("seen", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class IdentityCfg(C.Structure):
     """zr_identity_cfg."""
     _fields_ = [("slots", C.c_int), ("num_landmarks", C.c_int), ("aspect_w", C.c_int), ("aspect_h", C.c_int),
@@ -234,6 +240,7 @@ SIGNATURES = [
     ("zr_identity_compact_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zr_identity_commit_async", _I, [_P, _SZ, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
     ("zr_identity_enrol_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, _P, _P, _P]),
+    ("zr_identity_link_async", _I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _U32, C.c_float, _P, _P]),
     ("zr_identity_blend_async", _I, [_P, _SZ, _P, _P, _P, _P, _U32, _P, _P]),
     ("zr_identity_refine_async", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _U32, C.c_float, _P, _P]),
     ("zr_identity_quality_async", _I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -668,6 +668,23 @@ PYBIND11_MODULE(_zaru_host, m) {
         }, py::arg("gallery"), py::arg("max_samples") = 64, py::arg("update_threshold") = NAN, py::keep_alive<1, 2>())
         .def("gallery_refinement", &DeviceMultiTracker::gallery_refinement)
         .def("refined_total", &DeviceMultiTracker::refined_total)
+        // duplicate gallery rows merged from track evidence (None turns it off; NaN: the identity
+        // threshold; min_observations 0: canonical rows only, not a writer)
+        .def("set_identity_merging", [](DeviceMultiTracker &t, const py::object &gallery, uint32_t min_observations,
+                                        float link_threshold) {
+            t.set_identity_merging(gallery.is_none() ? nullptr : gallery.cast<Gallery *>(), min_observations, link_threshold);
+        }, py::arg("gallery"), py::arg("min_observations") = 3, py::arg("link_threshold") = NAN, py::keep_alive<1, 2>())
+        .def("identity_merging", [](const DeviceMultiTracker &t) -> py::object {
+            const auto m = t.identity_merging();
+            if (!m.on) return py::none();
+            py::dict d;
+            d["min_observations"] = m.min_observations;
+            d["link_threshold"] = m.link_threshold;
+            return d;
+        })
+        .def("merged_total", &DeviceMultiTracker::merged_total)
+        .def("merge_vetoed_total", &DeviceMultiTracker::merge_vetoed_total)
+        .def("merge_observed_total", &DeviceMultiTracker::merge_observed_total)
         // the face quality gate: FaceQualityGate tiers (learn: the embed tier when None); embed None: off
         .def("set_identity_quality", [](DeviceMultiTracker &t, const py::object &embed, const py::object &learn) {
             if (embed.is_none()) return t.set_identity_quality(nullptr);
@@ -1279,6 +1296,34 @@ PYBIND11_MODULE(_zaru_host, m) {
         })
         .def("set_row_updates", [](Gallery &g, const std::vector<uint32_t> &counts) { g.set_row_updates(counts); },
              py::arg("counts"))
+        // merged rows (DeviceMultiTracker.set_identity_merging): the canonical row of each row in use
+        // ([n] i32), its restore after add(), ids[aliases], the pending (partner [n] i32, seen [n] u32)
+        // records, and the manual merge (returns the canonical row)
+        .def("aliases", [](Gallery &g) {
+            const std::vector<int32_t> v = g.aliases();
+            py::array_t<int32_t> a((py::ssize_t)v.size());
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(int32_t));
+            return a;
+        })
+        .def("set_aliases", [](Gallery &g, const std::vector<int32_t> &aliases) { g.set_aliases(aliases); },
+             py::arg("aliases"))
+        .def("person_ids", [](Gallery &g) {
+            const std::vector<uint64_t> v = g.person_ids();
+            py::array_t<uint64_t> a((py::ssize_t)v.size());
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(uint64_t));
+            return a;
+        })
+        .def("pending_links", [](Gallery &g) {
+            std::vector<int32_t> partner;
+            std::vector<uint32_t> seen;
+            g.pending_links(partner, seen);
+            py::array_t<int32_t> p((py::ssize_t)partner.size());
+            py::array_t<uint32_t> s((py::ssize_t)seen.size());
+            if (!partner.empty()) std::memcpy(p.mutable_data(), partner.data(), partner.size() * sizeof(int32_t));
+            if (!seen.empty()) std::memcpy(s.mutable_data(), seen.data(), seen.size() * sizeof(uint32_t));
+            return py::make_tuple(p, s);
+        })
+        .def("merge_rows", &Gallery::merge_rows, py::arg("a"), py::arg("b"))
         .def("add", [](Gallery &g, py::array_t<float, py::array::c_style> rows, const std::vector<uint64_t> &ids) {
             if ((size_t)rows.size() != ids.size() * g.dim()) throw ZaruError(ZR_ERR_SHAPE, "rows must be [len(ids)][dim]");
             g.add(rows.data(), ids.data(), ids.size());

@@ -158,6 +158,10 @@ void DeviceMultiTracker::set_gallery_refinement(Gallery *gallery, uint32_t max_s
     identity_.set_refinement(ctx(), gallery, max_samples, update_threshold);
 }
 
+void DeviceMultiTracker::set_identity_merging(Gallery *gallery, uint32_t min_observations, float link_threshold) {
+    identity_.set_merging(ctx(), gallery, min_observations, link_threshold);
+}
+
 void DeviceMultiTracker::set_identity_quality(const zr_quality_tier *embed, const zr_quality_tier *learn) {
     export_.pending = false;  // a snapshot's arrays are those of the features it was taken with
     identity_.set_quality(ctx(), embed, learn);
@@ -329,6 +333,9 @@ uint64_t DeviceMultiTracker::identity_images() { return read_u64(identity_.total
 uint64_t DeviceMultiTracker::enrolled_total() { return read_u64(identity_.enrol_counts, 0); }
 uint64_t DeviceMultiTracker::enrol_dropped() { return read_u64(identity_.enrol_counts, 1); }
 uint64_t DeviceMultiTracker::refined_total() { return read_u64(identity_.refine_total); }
+uint64_t DeviceMultiTracker::merged_total() { return read_u64(identity_.merge_counts, 0); }
+uint64_t DeviceMultiTracker::merge_vetoed_total() { return read_u64(identity_.merge_counts, 1); }
+uint64_t DeviceMultiTracker::merge_observed_total() { return read_u64(identity_.merge_counts, 2); }
 uint64_t DeviceMultiTracker::quality_measured_total() { return read_u64(identity_.quality.counts, 0); }
 uint64_t DeviceMultiTracker::quality_rejected_total() { return read_u64(identity_.quality.counts, 1); }
 uint64_t DeviceMultiTracker::quality_held_back_total() { return read_u64(identity_.quality.counts, 2); }

@@ -129,6 +129,31 @@ class DeviceMultiTracker {
     void set_gallery_refinement(Gallery *gallery, uint32_t max_samples = 64, float update_threshold = NAN);
     bool gallery_refinement() const { return identity_.refine != nullptr; }
     uint64_t refined_total();   // contributions this tracker's steps applied, summed
+    // Merging duplicate gallery rows (zr_identity_link_async in include/zaru_hip.h has the rule).
+    // Enrolment only appends, so one person can own two rows and flicker between two ids.  A
+    // continuously tracked object is one person: when its nearest row at two successive looks is A,
+    // then B (both within `link_threshold`; NaN: the identity threshold as it is at each step), that is
+    // one observation of the pair, unless another object of the same frame holds A or B -- then they are
+    // two people and the pair's count starts over.  After `min_observations` the rows merge: neither
+    // moves, the person keeps both as templates, and every row a step reports -- identity rows in
+    // objects(), objects_packed() and snapshot() -- is the canonical (lowest) row of its person, so
+    // the person id is stable again.  `gallery` must be the reserved gallery set_recognition was given;
+    // nullptr turns merging off, as does every call of set_recognition.  The tracker is a writer of the
+    // gallery under the one-writer rule of set_enrolment; with min_observations == 0 it only reports
+    // canonical rows of a table another tracker (or Gallery::merge_rows) writes, and is no writer.
+    // Read the table with Gallery::aliases() / pending_links().
+    void set_identity_merging(Gallery *gallery, uint32_t min_observations = 3, float link_threshold = NAN);
+    struct IdentityMerging {
+        bool on;
+        uint32_t min_observations;
+        float link_threshold;
+    };
+    IdentityMerging identity_merging() const {
+        return {identity_.merge != nullptr, identity_.merge_min, identity_.merge_threshold};
+    }
+    uint64_t merged_total();         // pairs this tracker's steps merged, summed (0 before set_identity_merging)
+    uint64_t merge_vetoed_total();   // evidence rows vetoed by a second object in the frame
+    uint64_t merge_observed_total(); // evidence rows counted as observations
     // The face quality gate (MultiQuality in multi_stages.h; zr_identity_quality_async in
     // include/zaru_hip.h has the measurement): a due object whose crop misses `embed` is not embedded
     // this step and stays due; one that is embedded but misses `learn` (default: the embed tier) is

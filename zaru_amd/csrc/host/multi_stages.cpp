@@ -56,7 +56,8 @@ void MultiIdentity::set(const MultiCtx &c, const std::vector<uint8_t> &model, co
         emb = std::make_unique<FaceEmbedder>(model, c.device);  // throws before anything changes
     }
     c.synchronize();  // the last step's launches still read the network and the gallery
-    enrol = refine = nullptr;  // enrolment, refinement and smoothing belong to the gallery they were set for
+    // enrolment, refinement, merging and smoothing belong to the gallery they were set for
+    enrol = refine = merge = nullptr;
     template_cap = 1;
     quality.enabled = quality.ran = false;  // and the quality gate to the embedder
     align.enabled = false;                  // as the alignment's grid does
@@ -132,6 +133,26 @@ void MultiIdentity::set_refinement(const MultiCtx &c, Gallery *g, uint32_t max_s
     refine = g;
     refine_max = max_samples;
     refine_threshold = update_threshold;
+}
+
+void MultiIdentity::set_merging(const MultiCtx &c, Gallery *g, uint32_t min_observations, float link_threshold) {
+    if (!g) {
+        c.synchronize();
+        merge = nullptr;
+        return;
+    }
+    if (!on() || g != gallery)
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "merging needs the gallery set_recognition was given");
+    if (!g->reserved()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "merging needs a reserved gallery (Gallery::reserve)");
+    c.synchronize();
+    if (min_observations) {  // a writer (enrolment and refinement are on this gallery or off: set_recognition's)
+        g->begin_enrol(c.owner);  // throws while another tracker's writing steps may be in flight
+        g->end_enrol(c.owner);
+    }
+    if (zero_once(merge_counts, 3, c.stream)) check(zr_stream_synchronize(c.stream));
+    merge = g;
+    merge_min = min_observations;
+    merge_threshold = link_threshold;
 }
 
 void MultiIdentity::set_quality(const MultiCtx &c, const zr_quality_tier *embed, const zr_quality_tier *learn) {
@@ -254,6 +275,11 @@ void MultiIdentity::enqueue(const MultiCtx &c, const std::vector<zr_frame> &fram
                                       enrol->device_ids(), enrol->device_count(), enrol->device_next_id(),
                                       enrol->capacity(), EMBEDDING_DIM, enrol_min, enrol_counts.ptr,
                                       enrol_counts.ptr + 1, stream));
+    if (merge)  // last: this step's enrolled rows sit at their defaults, the refinement saw the nearest rows
+        check(zr_identity_link_async(&cfg, d_state, nv, d_src, learn_of, states[in].ptr, states[o].ptr,
+                                     merge->device_links(), merge->device_count(), merge->capacity(), merge_min,
+                                     std::isnan(merge_threshold) ? cfg.threshold : merge_threshold,
+                                     merge_counts.ptr, stream));
     flipped = !flipped;
     ran = true;
 }

@@ -91,7 +91,10 @@ struct MultiAlign {
 //   g. with set_smoothing: zr_identity_blend_async between c. and d. (the object's template: its
 //      stored embedding moved towards this step's), and d. and e. read the blended rows,
 //   h. with set_refinement: zr_identity_refine_async between e. and f. (each known object's
-//      gallery row moved towards its raw sample of this step; kernels/template.hip).
+//      gallery row moved towards its raw sample of this step; kernels/template.hip),
+//   i. with set_merging: zr_identity_link_async last of all (two rows one tracked object alternates
+//      between become one person, unless both are in the frame; every reported row becomes the
+//      canonical row of its person; kernels/link.hip).
 // The crop is taken from this step's frame at the place the previous frame's landmarks give: the
 // one frame of lag with which the tracker's own RoI is derived (step 1 consumes the previous
 // frame's estimate to place this frame's view).  With a filter set the crop follows the filtered
@@ -118,13 +121,18 @@ struct MultiIdentity {
     uint32_t refine_max = 64;
     float refine_threshold = NAN;        // NaN: the identity threshold at each step
     DeviceArray<uint64_t> refine_total;  // [0] contributions applied
+    Gallery *merge = nullptr;            // gallery, when merging of duplicate rows is on
+    uint32_t merge_min = 3;              // observations that merge a pair; 0: canonical rows only, not a writer
+    float merge_threshold = NAN;         // NaN: the identity threshold at each step
+    DeviceArray<uint64_t> merge_counts;  // [0] merged, [1] vetoed, [2] observed
     MultiQuality quality;                // the quality gate (off by default)
     MultiAlign align;                    // aligned crops (off by default)
 
     MultiIdentity();
     bool on() const { return embedder != nullptr; }
     bool has_result() const { return on() && ran; }
-    Gallery *written() const { return enrol ? enrol : refine; }  // the gallery this loop's steps write
+    // the gallery this loop's steps write
+    Gallery *written() const { return enrol ? enrol : refine ? refine : merge && merge_min ? merge : nullptr; }
     const DeviceArray<zr_identity_state> &state() const { return states[flipped ? 1 : 0]; }  // the current ones
     const DeviceArray<float> &emb() const { return embs[flipped ? 1 : 0]; }
     // DeviceMultiTracker::set_recognition / set_enrolment / set_identity_smoothing / set_gallery_refinement
@@ -132,6 +140,8 @@ struct MultiIdentity {
     void set_enrolment(const MultiCtx &c, Gallery *g, uint64_t first_id, uint32_t min_embeddings);
     void set_smoothing(uint32_t cap);
     void set_refinement(const MultiCtx &c, Gallery *g, uint32_t max_samples, float update_threshold);
+    // DeviceMultiTracker::set_identity_merging; nullptr: off
+    void set_merging(const MultiCtx &c, Gallery *g, uint32_t min_observations, float link_threshold);
     // DeviceMultiTracker::set_identity_quality; embed == nullptr: off.  Resets every object's record.
     void set_quality(const MultiCtx &c, const zr_quality_tier *embed, const zr_quality_tier *learn);
     // DeviceMultiTracker::set_identity_alignment; nullptr: off
@@ -140,7 +150,7 @@ struct MultiIdentity {
     const DeviceArray<zr_face_quality> &quality_state() const { return quality.recs[flipped ? 1 : 0]; }
     // a valid view in every entry of the packed crop table, as the loop's frame_size() does for its own
     void frame_size(const MultiCtx &c, const zr_view_desc &det_tmpl);
-    // a.-h.; the gallery's rows and size as they are now (Gallery::add may have reallocated them).
+    // a.-i.; the gallery's rows and size as they are now (Gallery::add may have reallocated them).
     // d_pose: this step's pose records, or nullptr (read by the quality gate only)
     void enqueue(const MultiCtx &c, const std::vector<zr_frame> &frames, double now_ms, const zr_track_state *d_state,
                  const float *d_landmarks, const int32_t *d_src, const zr_pose *d_pose);

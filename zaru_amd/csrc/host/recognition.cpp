@@ -183,6 +183,8 @@ void Gallery::reserve(size_t capacity) {
     dev_ids_.resize(capacity);
     updates_.resize(capacity);
     check(zr_memset_async(updates_.ptr, 0, capacity * sizeof(uint32_t), stream_));
+    links_.resize(capacity);
+    reset_links();
     const int32_t count = (int32_t)have;
     check(zr_memset_async(dev_ids_.ptr, 0, capacity * sizeof(uint64_t), stream_));
     if (have) check(zr_memcpy_async(dev_ids_.ptr, ids_.data(), have * sizeof(uint64_t), 0, stream_));
@@ -199,8 +201,88 @@ void Gallery::clear() {
     check(zr_memset_async(count_.ptr, 0, sizeof(int32_t), stream_));
     check(zr_memset_async(next_id_.ptr, 0, sizeof(uint64_t), stream_));
     check(zr_memset_async(updates_.ptr, 0, cap_ * sizeof(uint32_t), stream_));
+    reset_links();
     check(zr_stream_synchronize(stream_));
     enrolled_ = 0;
+}
+
+void Gallery::reset_links() {
+    std::vector<zr_gallery_link> def(cap_);
+    for (size_t r = 0; r < cap_; r++) def[r] = zr_gallery_link{(int32_t)r, -1, 0u, 0u};
+    check(zr_memcpy_async(links_.ptr, def.data(), cap_ * sizeof(zr_gallery_link), 0, stream_));
+    check(zr_stream_synchronize(stream_));  // `def` is pageable and goes out of scope
+}
+
+std::vector<zr_gallery_link> Gallery::read_links() {
+    if (!reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is not reserved");
+    refresh();
+    std::vector<zr_gallery_link> l(ids_.size());
+    if (l.empty()) return l;
+    check(zr_memcpy_async(l.data(), links_.ptr, l.size() * sizeof(zr_gallery_link), 1, stream_));
+    check(zr_stream_synchronize(stream_));
+    // what the device reads: an alias outside [0, r] is the row itself
+    for (size_t r = 0; r < l.size(); r++)
+        if (l[r].alias < 0 || (size_t)l[r].alias > r) l[r].alias = (int32_t)r;
+    return l;
+}
+
+void Gallery::write_links(const std::vector<zr_gallery_link> &l) {
+    if (l.empty()) return;
+    check(zr_memcpy_async(links_.ptr, l.data(), l.size() * sizeof(zr_gallery_link), 0, stream_));
+    check(zr_stream_synchronize(stream_));
+}
+
+std::vector<int32_t> Gallery::aliases() {
+    const auto l = read_links();
+    std::vector<int32_t> a(l.size());
+    for (size_t r = 0; r < l.size(); r++) a[r] = l[r].alias;
+    return a;
+}
+
+void Gallery::set_aliases(const std::vector<int32_t> &aliases) {
+    if (!reserved_) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "the gallery is not reserved");
+    refresh();
+    if (aliases.size() != ids_.size()) throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "one alias per row in use");
+    for (size_t r = 0; r < aliases.size(); r++) {
+        const int32_t a = aliases[r];
+        if (a < 0 || (size_t)a > r || aliases[(size_t)a] != a)
+            throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "an alias must be a canonical row at or below its own row");
+    }
+    std::vector<zr_gallery_link> l(aliases.size());
+    for (size_t r = 0; r < l.size(); r++) l[r] = zr_gallery_link{aliases[r], -1, 0u, 0u};
+    write_links(l);
+}
+
+std::vector<uint64_t> Gallery::person_ids() {
+    const auto l = read_links();
+    std::vector<uint64_t> ids(l.size());
+    for (size_t r = 0; r < l.size(); r++) ids[r] = ids_[(size_t)l[r].alias];
+    return ids;
+}
+
+void Gallery::pending_links(std::vector<int32_t> &partner, std::vector<uint32_t> &seen) {
+    const auto l = read_links();
+    partner.resize(l.size());
+    seen.resize(l.size());
+    for (size_t r = 0; r < l.size(); r++) {
+        partner[r] = l[r].partner;
+        seen[r] = l[r].seen;
+    }
+}
+
+int32_t Gallery::merge_rows(int32_t a, int32_t b) {
+    auto l = read_links();
+    if (a < 0 || b < 0 || (size_t)a >= l.size() || (size_t)b >= l.size())
+        throw ZaruError(ZR_ERR_INVALID_ARGUMENT, "merge_rows: a row outside the rows in use");
+    const int32_t ca = l[(size_t)a].alias, cb = l[(size_t)b].alias;
+    const int32_t lo = std::min(ca, cb), hi = std::max(ca, cb);
+    if (lo == hi) return lo;
+    for (auto &rec : l)
+        if (rec.alias == hi) rec.alias = lo;
+    l[(size_t)hi].partner = -1;
+    l[(size_t)hi].seen = 0;
+    write_links(l);
+    return lo;
 }
 
 std::vector<uint32_t> Gallery::row_updates() {

@@ -130,8 +130,28 @@ class Gallery {
     uint32_t *device_updates() { return updates_.ptr; }
     std::vector<uint32_t> row_updates();
     void set_row_updates(const std::vector<uint32_t> &counts);
-    // One writing tracker (enrolling or refining) at a time: a tracker announces the steps it enqueues
-    // (begin) and that it has synchronised (end).  begin throws while another owner's steps may
+    // Merged rows (DeviceMultiTracker::set_identity_merging; zr_identity_link_async in
+    // include/zaru_hip.h has the rule): a reserved gallery keeps one zr_gallery_link per row of its
+    // capacity on the device.  Rows are never moved or removed; a row's alias is the canonical row of
+    // its person, and id_of(alias) is the person's id.  reserve() and clear() write the default record
+    // {r, -1, 0, 0} to every row, and a row at or past the count always holds its default, so add() and
+    // enrolment leave the table alone.  All of these throw for an unreserved gallery and refresh first;
+    // call them, like row_updates(), after the writing tracker's synchronize().
+    zr_gallery_link *device_links() { return links_.ptr; }
+    std::vector<int32_t> aliases();  // one per row in use
+    // one alias per row in use, 0 <= a[r] <= r and a[a[r]] == a[r] (else ZR_ERR_INVALID_ARGUMENT);
+    // resets the pending partner / seen records: with rows() what a saved gallery is loaded from
+    void set_aliases(const std::vector<int32_t> &aliases);
+    // ids[aliases]: what a fresh gallery's add() takes to become a plain multi-template gallery
+    // (several rows with one id) for FaceRecognizer and match()
+    std::vector<uint64_t> person_ids();
+    void pending_links(std::vector<int32_t> &partner, std::vector<uint32_t> &seen);
+    // the manual merge, by the device's relabel: the lower canonical row wins, the table stays flat,
+    // the higher canonical row's pending record is cleared.  Returns the canonical row; throws for a
+    // row outside the rows in use
+    int32_t merge_rows(int32_t a, int32_t b);
+    // One writing tracker (enrolling, refining or merging) at a time: a tracker announces the steps it
+    // enqueues (begin) and that it has synchronised (end).  begin throws while another owner's steps may
     // still be in flight.
     void begin_enrol(const void *owner);
     void end_enrol(const void *owner);
@@ -148,6 +168,10 @@ class Gallery {
     DeviceArray<int32_t> count_;
     DeviceArray<uint64_t> dev_ids_, next_id_;
     DeviceArray<uint32_t> updates_;  // [cap_] samples taken per row (reserved galleries only)
+    DeviceArray<zr_gallery_link> links_;  // [cap_] the rows' link records (reserved galleries only)
+    void reset_links();                   // the default record in every row; enqueued on stream_
+    std::vector<zr_gallery_link> read_links();  // of the rows in use (refreshes)
+    void write_links(const std::vector<zr_gallery_link> &l);
 };
 
 struct Recognition {

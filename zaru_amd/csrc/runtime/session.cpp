@@ -1323,6 +1323,51 @@ int zr_identity_enrol_async(const zr_identity_cfg *cfg, size_t n, const int32_t 
     });
 }
 
+// ---- duplicate gallery rows merged from track evidence (kernels/link.hip)
+static_assert(sizeof(zr_gallery_link) == sizeof(zr::GalleryLink) && sizeof(zr_gallery_link) == 16,
+              "zr_gallery_link layout");
+static_assert(offsetof(zr_gallery_link, partner) == offsetof(zr::GalleryLink, partner) &&
+                  offsetof(zr_gallery_link, seen) == offsetof(zr::GalleryLink, seen),
+              "zr_gallery_link layout");
+
+int zr_identity_link_async(const zr_identity_cfg *cfg, const zr_track_state *d_state, size_t n,
+                           const int32_t *d_src, const int32_t *d_due_of, const zr_identity_state *d_in,
+                           zr_identity_state *d_out, zr_gallery_link *d_links, const int32_t *d_count,
+                           size_t capacity, uint32_t min_observations, float link_threshold, uint64_t *d_counts,
+                           void *hip_stream) {
+    return guarded([&]() -> int {
+        if (!cfg || !d_state || !d_src || !d_due_of || !d_in || !d_out || !d_links || !d_count)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "null argument");
+        if (n == 0 || n > (1u << 24)) return set_err(ZR_ERR_INVALID_ARGUMENT, "n must be 1..2^24");
+        if (cfg->slots < 1 || cfg->slots > 64 || n % (size_t)cfg->slots != 0)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "slots must be 1..64 and divide n");
+        if (capacity < 1 || capacity > 0x7fffffffu) return set_err(ZR_ERR_INVALID_ARGUMENT, "capacity must be 1..2^31-1");
+        if (d_in == d_out)
+            return set_err(ZR_ERR_INVALID_ARGUMENT, "the input identity state must be a buffer of its own");
+        zr::IdentityLinkParams p{};
+        p.state = reinterpret_cast<const zr::TrackState *>(d_state);
+        p.src = d_src;
+        p.due_of = d_due_of;
+        p.in = reinterpret_cast<const zr::IdentityState *>(d_in);
+        p.out = reinterpret_cast<zr::IdentityState *>(d_out);
+        p.links = reinterpret_cast<zr::GalleryLink *>(d_links);
+        p.count = d_count;
+        p.counts = d_counts;
+        p.n = (int)n;
+        p.K = cfg->slots;
+        p.capacity = (int)capacity;
+        p.min_observations = min_observations;
+        p.threshold = link_threshold;
+        if (min_observations != 0) {  // 0: this caller only reads a table another one writes
+            zr::launch_identity_link_walk(p, (hipStream_t)hip_stream);
+            HIP_TRY(hipGetLastError());
+        }
+        zr::launch_identity_link_canon(p, (hipStream_t)hip_stream);
+        HIP_TRY(hipGetLastError());
+        return ZR_OK;
+    });
+}
+
 // ---- templates and refined gallery rows (kernels/template.hip)
 int zr_identity_blend_async(const zr_identity_cfg *cfg, size_t n, const int32_t *d_due_of,
                             const zr_identity_state *d_state_out, const float *d_emb_out, const float *d_dense_emb,

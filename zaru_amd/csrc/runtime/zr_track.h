@@ -326,6 +326,29 @@ struct IdentityRefineParams {
     float threshold;
 };
 const char *launch_identity_refine(const IdentityRefineParams &p, hipStream_t s);
+// Merging duplicate gallery rows (kernels/link.hip), last in the identity leg.  Layout mirrored by
+// zr_gallery_link in include/zaru_hip.h.
+struct GalleryLink {
+    int32_t alias;     // canonical row of this row's person, <= own row
+    int32_t partner;   // on a canonical row: the lower canonical row it is suspected to be, -1: none
+    uint32_t seen;     // observations of (partner, this row) so far
+    uint32_t reserved;
+};
+struct IdentityLinkParams {
+    const TrackState *state;  // [n]
+    const int32_t *src;       // [n] as IdentitySelectParams::src
+    const int32_t *due_of;    // [n] the list refine and enrol read
+    const IdentityState *in;  // [n] the states select gathered from
+    IdentityState *out;       // [n] the committed states; pass 2 rewrites rows that are not canonical
+    GalleryLink *links;       // [capacity] in / out
+    const int32_t *count;     // rows in the gallery
+    uint64_t *counts;         // [3] in / out: += merged, vetoed, observed; may be null
+    int n, K, capacity;
+    uint32_t min_observations;
+    float threshold;
+};
+const char *launch_identity_link_walk(const IdentityLinkParams &p, hipStream_t s);   // pass 1: one workgroup
+const char *launch_identity_link_canon(const IdentityLinkParams &p, hipStream_t s);  // pass 2: grid-wide
 
 // Eye refinement of the tracked faces (kernels/eye.hip): entry 2i is row i's left eye, 2i + 1 its
 // right eye.  The packing between select and crop is identity_compact_kernel over the 2n entries.

@@ -31,6 +31,11 @@ groups, ow=112, oh=112, max_residual=inf)``; ``None``: off) replaces every due o
 five-point similarity crop, rotated by the roll of the head; ``aligned_total()`` / ``align_fallback_total()``
 count, ``aligned_crop_view(landmarks, image_w, image_h, alignment)`` gives ``(ViewData | None, record)`` on
 the host and ``FaceEmbedder.embed_views(image, views)`` embeds such views.
+Merged people: ``set_identity_merging(gallery, min_observations=3, link_threshold=nan)`` (``None``: off; 0
+observations: report canonical rows only) joins two gallery rows that one tracked object alternates between,
+unless both are in the frame; ``Gallery.aliases()`` / ``set_aliases(list)`` / ``person_ids()`` /
+``pending_links()`` / ``merge_rows(a, b)`` read and write the table, ``merged_total()`` /
+``merge_vetoed_total()`` / ``merge_observed_total()`` count.
 
 Tiled detection, for the small faces of a large frame: ``detection_tiles(width, height, cols, rows,
 overlap=0.25, include_full=True)`` gives the rects, ``TiledDetector(network, tiles)`` is the host
